@@ -5,24 +5,30 @@ audio frames/sec training).
 One "step" = one full optimiser step of the reference's training loop (bin/train_asr.py:95-137,
 src/solver.py:76-91): forward (encoder -> CTC head [-> attention decoder]) + losses + backward +
 [gradient all-reduce] + clip_grad_norm_(5.0) + Adadelta step, on a synthetic LibriSpeech-shaped
-batch that is already resident in HBM.  Default workload = BASELINE.json configs[2] ("cfg3", the
+batch that is already resident in HBM.  Every step starts from the same seeded weights and empty optimiser state
+(restored between steps, outside the timed interval), so every run computes the same step; `loss` / `grad_norm` and
+--dump-outputs are what that step gives.  Default workload = BASELINE.json configs[2] ("cfg3", the
 configuration the metric is quoted on: full LAS, 4 x pBLSTM-1024 [2,2,2,1] concat + location-aware
 attention + LSTM-1024 decoder + CTC hybrid lambda 0.5, B=32 x T=1600 x 80-mel, V=5000, L=64);
 `--workload cfg2` = configs[1] (2 x pBLSTM-512, CTC-only, T=1000).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full --dump-outputs out/   # + every other figure; + outputs
     python bench.py --gpus N ...          # no WORLD_SIZE in the environment: bench.py starts the N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # the driver's form
 
 One process per GPU (rank r on GPU r), RCCL through torch.distributed ("nccl").  The N-rank line carries RCCL's own
-view of the job (`rccl`: world size, the all-reduced sum of the ranks, exposed all-reduce ms per step).
+view of the job (`rccl`: world size, the all-reduced sum of the ranks; with --full the exposed all-reduce ms per step).
 
-Rank 0 prints ONE JSON line (its last line of stdout).  `roofline` is for the dominant kernel by time (the bf16x6
-split GEMM), measured with hipEvents on the launch streams INSIDE the timed region; `roofline_recurrence` (the
-persistent LSTM recurrence kernels: latency-bound dependent chain), `roofline_hbm` (the HBM-bound kernels: split
-passes, optimiser, CTC gradient, feature front end, against 8 TB/s) and `kernel_families` come from hipEvents over a
-few extra untimed steps right after the region (an event pair costs ~3 us of stream time: all families together were
-1 ms per cfg3 step); `cpu_baseline` times the CPU oracle (a port of the reference's --cpu arithmetic) on the host cores.
+Rank 0 prints ONE JSON line (its last line of stdout).  A plain run sets up, warms up, times --steps steps and prints
+the headline (`value`, `ms_per_step`, ...); nothing else runs on the GPU or the host.  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (see write_outputs).  --full adds everything else, measured as before:
+`roofline` is for the dominant kernel by time (the bf16x6 split GEMM), measured with hipEvents on the launch streams
+INSIDE the timed region; `roofline_recurrence` (the persistent LSTM recurrence kernels: latency-bound dependent chain),
+`roofline_hbm` (the HBM-bound kernels: split passes, optimiser, CTC gradient, feature front end, against 8 TB/s) and
+`kernel_families` come from hipEvents over a few extra untimed steps right after the region (an event pair costs ~3 us
+of stream time: all families together were 1 ms per cfg3 step); `exact_f32_mfma` re-times the step without operand
+splitting; `cpu_baseline` times the CPU oracle (a port of the reference's --cpu arithmetic) on the host cores.
 """
 import argparse
 import importlib
@@ -213,11 +219,14 @@ def _cpu_baseline_worker(workload, steps, threads, probe):
 
 def cpu_baseline(workload, budget_s=480):
     """full batch, >= 1 warm-up + 3 timed steps, thread count = the fastest of {32, 64, all host
-    cores}, stated.  Every candidate is probed in its own subprocess under a timeout (ATen's CPU LSTM can take
-    minutes at hundreds of threads); then the timed run, bounded by `budget_s`.  Returns the last JSON line the
-    worker printed."""
+    cores}, none above OMP_NUM_THREADS, stated.  Every candidate is probed in its own subprocess under a timeout
+    (ATen's CPU LSTM can take minutes at hundreds of threads); then the timed run, bounded by `budget_s`.  Returns
+    the last JSON line the worker printed."""
     import subprocess
     ncpu = os.cpu_count() or 1
+    # an OMP_NUM_THREADS set by the environment is the number of CPUs this job may use: more threads only
+    # oversubscribe them (and the probes of larger counts would each run into their time limit)
+    ncpu = min(ncpu, int(os.environ.get("OMP_NUM_THREADS") or ncpu))
     me = [sys.executable, os.path.abspath(__file__), "--workload", workload]
     probe, limit = {}, 90.0
     for t in sorted({min(32, ncpu), min(64, ncpu), ncpu}):
@@ -361,7 +370,8 @@ def frontend_rate(lib, w, device, reps=5):
 
 def build_step(workload, device, dist=None, rank=0, force_collectives=False):
     """model + one full optimiser step (forward, CTC/CE losses, backward, clip, Adadelta) on a
-    resident synthetic batch of `workload`; returns (model, step) with step() -> (loss, grad_norm)"""
+    resident synthetic batch of `workload`; returns (model, step) with step() -> (loss, grad_norm) and
+    step.reset(), which puts the model and the optimiser back into their seeded initial state"""
     ops = importlib.import_module(PKG + ".ops")
     w = WORKLOADS[workload]
     model = build_model(w, device)
@@ -373,15 +383,26 @@ def build_step(workload, device, dist=None, rank=0, force_collectives=False):
     opt = importlib.import_module(PKG + ".fused_optim").FusedAdadelta(params, lr=1.0, eps=1e-8)
     ctc_loss_fn = ops.CTCLoss(blank=0)
     ce_loss_fn = ops.CrossEntropyLoss(ignore_index=0) if model.enable_att else None
+    initial = [p.detach().clone() for p in params]
+
+    def reset():
+        """the weights the model was built with and empty Adadelta accumulators (as before the first step)"""
+        with torch.no_grad():
+            torch._foreach_copy_(params, initial)
+            for st in opt.state.values():
+                torch._foreach_zero_([st["square_avg"], st["acc_delta"]])
+                st["step"].zero_()
 
     feat, feat_len, txt = synth(w, seed=rank, device=device)    # per-rank data, same model seed
     txt_len = torch.sum(txt != 0, dim=-1)
     L = int(txt_len.max())
     n_tok_local = txt_len.sum().to(torch.float32)
+    last = {}
 
     def step():
         opt.zero_grad(set_to_none=True)
         ctc_out, enc_len, att_out, _, _ = model(feat, feat_len, L, tf_rate=1.0, teacher=txt)
+        last["ctc_output"], last["att_output"] = ctc_out, att_out
         total = 0
         if ctc_out is not None:
             total = total + ctc_loss_fn(ctc_out.transpose(0, 1), txt, enc_len, txt_len) * model.ctc_weight
@@ -416,8 +437,68 @@ def build_step(workload, device, dist=None, rank=0, force_collectives=False):
         return float(total.detach()), sq ** 0.5
 
     step.probe = probe
+    step.reset = reset
     step.engine = engine
+    step.last = last                     # the forward outputs of the latest step() (None where the model has no head)
     return model, step
+
+
+# --dump-outputs: at most DUMP_LIMIT_BYTES in all.  An array longer than its cap is replaced by a fixed sample of its
+# flattened elements (indices drawn with replacement by a CPU generator seeded with DUMP_SEED, sorted): the same
+# shape gives the same indices in every run, so two builds can be compared element for element.
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 0
+DUMP_CAP = 1 << 20             # elements of a step output (CTC log-probabilities, decoder logits)
+DUMP_CAP_PARAMS = 1 << 22      # elements of the parameter vector
+
+
+def training_outputs(model, step, loss, grad_norm):
+    """name -> (tensor, cap): what the last timed training step returned (loss, gradient norm before clipping), what
+    the model's forward handed it, and the parameters it left behind as one flattened vector (named_parameters()
+    order).  One vector, not one array per tensor: a tensor whose gradient is zero but for rounding (the bias in front
+    of a softmax) holds nothing but rounding after the update, and only the scale of all the weights says how large"""
+    arrays = {"loss": (loss.detach(), DUMP_CAP), "grad_norm": (torch.as_tensor(grad_norm).detach(), DUMP_CAP)}
+    for name, t in step.last.items():
+        if t is not None:
+            arrays[name] = (t.detach(), DUMP_CAP)
+    arrays["params"] = (torch.cat([p.detach().reshape(-1) for p in model.parameters()]), DUMP_CAP_PARAMS)
+    return arrays
+
+
+def decode_outputs(hyps):
+    """name -> (float64 array, cap) of what the last timed decode batch returned: for every utterance its hypotheses
+    ordered by token sequence (hypotheses of equal score come back in either order), token ids (-1 past the end) and
+    per-token scores (NaN past the end; they also give the ranking)"""
+    import numpy as np
+    K = max((len(h) for h in hyps), default=0)
+    n = max((len(x.output_seq) for h in hyps for x in h), default=0)
+    tok, sc = np.full((len(hyps), K, n), -1.0), np.full((len(hyps), K, n), np.nan)
+    for u, h in enumerate(hyps):
+        for k, x in enumerate(sorted(h, key=lambda x: x.outIndex)):
+            tok[u, k, :len(x.output_seq)] = x.outIndex
+            sc[u, k, :len(x.output_scores)] = [float(s) for s in x.output_scores]
+    return {"hyp_tokens": (tok, DUMP_CAP), "hyp_token_scores": (sc, DUMP_CAP)}
+
+
+def write_outputs(dirname, arrays):
+    """arrays: name -> (tensor or array, cap) -> dirname/<name>.npy, float64 kept, every other dtype as float32; an
+    array within its cap keeps its shape, a sample is flat"""
+    import numpy as np
+    out = {}
+    for name, (t, cap) in arrays.items():
+        t = torch.as_tensor(t)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        out[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------ cfg5 (decode)
@@ -494,36 +575,38 @@ def decode_main(args, rank, world, device, dist):
             tt = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if args.dump_outputs and rank == 0:
+            write_outputs(args.dump_outputs, decode_outputs(hyps))
         n_dec = max(len(h[0].outIndex) for h in hyps)             # decode steps of the batch = its longest hypothesis
-        # launches per decode step: the library's own count over one more batch (every family's hooks on)
-        import ctypes
-        lib.asrk_profile_reset()
-        lib.asrk_profile_families(0xffffffff)
-        lib.asrk_profile_enable(1)
-        dec.forward_batch(feat, flen)
-        torch.cuda.synchronize()
-        lib.asrk_profile_enable(0)
-        launches = 0
-        for idx in range(13):
-            ms, n = ctypes.c_double(0), ctypes.c_int64(0)
-            lib.asrk_profile_get(idx, ctypes.byref(ms), ctypes.byref(n))
-            launches += n.value
-        # one utterance at a time (the reference's batch = 1 decoding, src/decode.py:64): reported beside the headline
-        f1, l1 = feat[:1], flen[:1]
-        dec(f1, l1)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(3):
-            h1 = dec(f1, l1)
-        torch.cuda.synchronize()
-        dt1 = (time.perf_counter() - t1) / 3
+        if args.full:
+            # launches per decode step: the library's own count over one more batch (every family's hooks on)
+            import ctypes
+            lib.asrk_profile_reset()
+            lib.asrk_profile_families(0xffffffff)
+            lib.asrk_profile_enable(1)
+            dec.forward_batch(feat, flen)
+            torch.cuda.synchronize()
+            lib.asrk_profile_enable(0)
+            launches = 0
+            for idx in range(13):
+                ms, n = ctypes.c_double(0), ctypes.c_int64(0)
+                lib.asrk_profile_get(idx, ctypes.byref(ms), ctypes.byref(n))
+                launches += n.value
+            # one utterance at a time (the reference's batch = 1 decoding, src/decode.py:64): reported beside the
+            # headline
+            f1, l1 = feat[:1], flen[:1]
+            dec(f1, l1)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(3):
+                h1 = dec(f1, l1)
+            torch.cuda.synchronize()
+            dt1 = (time.perf_counter() - t1) / 3
     if rank != 0:
         return
     Te = T // 8                                                    # cfg3 encoder: time reduced by 2 * 2 * 2 * 1
     ms_step = dt / args.steps * 1e3
     ms_dec = ms_step / n_dec
-    bytes_dec = cfg5_bytes_per_decode_step(w, U, Te)
-    gbs = bytes_dec / (ms_dec * 1e-3) / 1e9
     out = {
         "metric": "joint CTC-attention beam-search decode (beam 16) + RNN-LM shallow fusion",
         "value": world * U * args.steps / dt, "unit": "utt/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -533,21 +616,26 @@ def decode_main(args, rank, world, device, dist):
         "config": {"workload": "cfg5: %d utterances of %d frames (8 s) per device batch, %s, cfg3 acoustic model + "
                                "2xLSTM-1024 LM, V=5000" % (U, T, json.dumps(CFG5_DECODE)),
                    "parallelism": "replicas x%d (utterances sharded over ranks, no data-path collective)" % world,
-                   "decode_steps_per_batch": n_dec, "ms_per_decode_step": ms_dec,
-                   "launches_per_decode_step": launches / n_dec,
-                   "one_utterance_at_a_time": {"s_per_utt": dt1, "utt_per_s": 1.0 / dt1, "rtf": dt1 / (T * 0.01),
-                                               "ms_per_decode_step": dt1 * 1e3 / len(h1[0].outIndex)}},
-        "roofline": {"kernel": "one decode position of the batch (decoder / LM cells and the vocabulary projections - "
-                               "bf16x6 panel GEMMs against weight panels split once at >= 128 live rows, weight-streaming "
-                               "skinny kernels below; attention over the utterances' key / value memory; prefix scores; "
-                               "radix top-k; the beam bookkeeping on the device): every operand is read once per position",
-                     "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
-                     "traffic": None, "bytes_per_decode_step": bytes_dec,
-                     "note": "a decode position is a chain of ~%d dependent library launches (plus the gathers between "
-                             "them) with no read-back: latency- and launch-bound, not bandwidth-bound; the host looks at "
-                             "the number of unfinished utterances every 8th position" % round(launches / n_dec)},
+                   "decode_steps_per_batch": n_dec, "ms_per_decode_step": ms_dec},
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        bytes_dec = cfg5_bytes_per_decode_step(w, U, Te)
+        gbs = bytes_dec / (ms_dec * 1e-3) / 1e9
+        out["config"].update({"launches_per_decode_step": launches / n_dec,
+                              "one_utterance_at_a_time": {"s_per_utt": dt1, "utt_per_s": 1.0 / dt1,
+                                                          "rtf": dt1 / (T * 0.01),
+                                                          "ms_per_decode_step": dt1 * 1e3 / len(h1[0].outIndex)}})
+        out["roofline"] = {
+            "kernel": "one decode position of the batch (decoder / LM cells and the vocabulary projections - bf16x6 "
+                      "panel GEMMs against weight panels split once at >= 128 live rows, weight-streaming skinny "
+                      "kernels below; attention over the utterances' key / value memory; prefix scores; radix top-k; "
+                      "the beam bookkeeping on the device): every operand is read once per position",
+            "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
+            "traffic": None, "bytes_per_decode_step": bytes_dec,
+            "note": "a decode position is a chain of ~%d dependent library launches (plus the gathers between them) "
+                    "with no read-back: latency- and launch-bound, not bandwidth-bound; the host looks at the number "
+                    "of unfinished utterances every 8th position" % round(launches / n_dec)}
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import beam_oracle as BO          # checker-side code: CPU baseline leg only
         sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
         torch.set_num_threads(min(args.cpu_threads, os.cpu_count() or 1))
@@ -620,9 +708,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS) + ["cfg5"],
                     help="cfg2 / cfg3 / shipped / cnn: training step (frames/s); cfg5: beam-search decode (utt/s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel-family / roofline figures (hipEvents inside the timed region and "
+                         "over extra steps), the exact-f32-MFMA cross-check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-exact-check", action="store_true",
-                    help="skip the exact-f32-MFMA cross-check (loss / gradient norm / step time without operand splitting)")
+                    help="with --full: skip the exact-f32-MFMA cross-check (loss / gradient norm / step time without "
+                         "operand splitting)")
     ap.add_argument("--cpu-baseline-only", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=32)
@@ -633,6 +727,8 @@ def main():
                     help="exercise the N-rank launch path without GPUs (gloo): ranks rendezvous, all-reduce their "
                          "rank numbers, rank 0 prints the line skeleton")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.print_kernel_digest:
         print("conv " + conv_source_digest())
         print(kernel_source_digest())             # last line: what tools/pmc_hbm.sh stamps as kernel_source_digest
@@ -681,25 +777,9 @@ def main():
 
     comm = comm_selfcheck(dist, rank, world, device) if dist is not None else None
     for _ in range(args.warmup):
+        step.reset()
         step()
     ops.check_errors()
-    if step.engine is not None:
-        step.engine.timing = True
-
-    # hipEvents around Encoder.forward (the north-star names the encoder forward)
-    enc_events = []
-
-    def _enc_pre(mod, inp):
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        enc_events.append([ev, None])
-
-    def _enc_post(mod, inp, out):
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        enc_events[-1][1] = ev
-
-    hooks = [model.encoder.register_forward_pre_hook(_enc_pre), model.encoder.register_forward_hook(_enc_post)]
 
     def fence():
         torch.cuda.synchronize()
@@ -707,59 +787,120 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # hipEvents inside the TIMED region: the dominant kernel's family (the GEMMs, roofline.achieved) only.  An event
-    # pair costs ~3 us of stream time (its marker packet waits for the kernel in front of it): all ~180 pairs of a cfg3
-    # step were measured at 1.0 ms per step (103.0 vs 104.0 ms), so the other families are timed in PROF_STEPS extra,
-    # untimed steps right after the region (same process, same tensors).
-    import ctypes
-    GEMM_FAMILIES = (1 << 0) | (1 << 8)
-    lib.asrk_profile_reset()
-    lib.asrk_profile_families(GEMM_FAMILIES)
-    lib.asrk_profile_enable(1)
+    if args.full:
+        if step.engine is not None:
+            step.engine.timing = True
+
+        # hipEvents around Encoder.forward (the north-star names the encoder forward)
+        enc_events = []
+
+        def _enc_pre(mod, inp):
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            enc_events.append([ev, None])
+
+        def _enc_post(mod, inp, out):
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            enc_events[-1][1] = ev
+
+        hooks = [model.encoder.register_forward_pre_hook(_enc_pre), model.encoder.register_forward_hook(_enc_post)]
+
+        # hipEvents inside the TIMED region: the dominant kernel's family (the GEMMs, roofline.achieved) only.  An event
+        # pair costs ~3 us of stream time (its marker packet waits for the kernel in front of it): all ~180 pairs of a
+        # cfg3 step were measured at 1.0 ms per step (103.0 vs 104.0 ms), so the other families are timed in PROF_STEPS
+        # extra, untimed steps right after the region (same process, same tensors).
+        import ctypes
+        GEMM_FAMILIES = (1 << 0) | (1 << 8)
+        lib.asrk_profile_reset()
+        lib.asrk_profile_families(GEMM_FAMILIES)
+        lib.asrk_profile_enable(1)
+    # Every step starts from the seeded initial state (step.reset: weights and optimiser accumulators restored on the
+    # launch stream before the step, outside its time): a step that went on from the weights of the one before would
+    # carry the rounding of the previous steps' atomically summed gradients with it, and over a few steps of Adadelta
+    # that grows far beyond rounding, so the last step would compute something else in every run.  A step's time is
+    # taken with hipEvents on the launch stream around it (the side streams fork from and join back into it).
+    marks = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     fence()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for e0, e1 in marks:
+        step.reset()
+        e0.record()
         loss, gn = step()
+        e1.record()
     fence()
-    dt = time.perf_counter() - t0
-    lib.asrk_profile_enable(0)
+    dt = sum(e0.elapsed_time(e1) for e0, e1 in marks) * 1e-3
+    if args.full:
+        lib.asrk_profile_enable(0)
     ops.check_errors()
-    for h in hooks:
-        h.remove()
-    enc_ms = sum(a.elapsed_time(b) for a, b in enc_events) / max(1, len(enc_events))
     if dist is not None:
         tt = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, training_outputs(model, step, loss, gn))
 
-    def read_families(ids, n_steps, with_work=False):
-        res = {}
-        for name, idx in ids:
-            ms, n, wk = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_double(0)
-            lib.asrk_profile_get(idx, ctypes.byref(ms), ctypes.byref(n))
-            lib.asrk_profile_get_work(idx, ctypes.byref(wk))
-            res[name] = {"ms_per_step": ms.value / n_steps, "launches_per_step": n.value / n_steps,
-                         "_work_per_step": wk.value / n_steps}
-        return res
+    if args.full:
+        for h in hooks:
+            h.remove()
+        enc_ms = sum(a.elapsed_time(b) for a, b in enc_events) / max(1, len(enc_events))
 
-    fam = read_families((("gemm", 0), ("gemm_bg", 8)), args.steps)
-    PROF_STEPS = max(1, min(args.steps, 5))
-    lib.asrk_profile_reset()
-    lib.asrk_profile_families(0xffffffff & ~GEMM_FAMILIES)
-    lib.asrk_profile_enable(1)
-    for _ in range(PROF_STEPS):
-        step()
-    fence()
-    lib.asrk_profile_enable(0)
-    lib.asrk_profile_families(0xffffffff)
-    fam.update(read_families((("lstm_fwd", 1), ("lstm_bwd", 2), ("ctc", 3), ("rowops", 4), ("attn", 5), ("cell", 6),
-                              ("speller", 9), ("conv", 10), ("split", 11), ("optim", 12), ("conv_mfma", 13)), PROF_STEPS))
+        def read_families(ids, n_steps, with_work=False):
+            res = {}
+            for name, idx in ids:
+                ms, n, wk = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_double(0)
+                lib.asrk_profile_get(idx, ctypes.byref(ms), ctypes.byref(n))
+                lib.asrk_profile_get_work(idx, ctypes.byref(wk))
+                res[name] = {"ms_per_step": ms.value / n_steps, "launches_per_step": n.value / n_steps,
+                             "_work_per_step": wk.value / n_steps}
+            return res
+
+        fam = read_families((("gemm", 0), ("gemm_bg", 8)), args.steps)
+        PROF_STEPS = max(1, min(args.steps, 5))
+        lib.asrk_profile_reset()
+        lib.asrk_profile_families(0xffffffff & ~GEMM_FAMILIES)
+        lib.asrk_profile_enable(1)
+        for _ in range(PROF_STEPS):
+            step.reset()
+            step()
+        fence()
+        lib.asrk_profile_enable(0)
+        lib.asrk_profile_families(0xffffffff)
+        fam.update(read_families((("lstm_fwd", 1), ("lstm_bwd", 2), ("ctc", 3), ("rowops", 4), ("attn", 5), ("cell", 6),
+                                  ("speller", 9), ("conv", 10), ("split", 11), ("optim", 12), ("conv_mfma", 13)),
+                                 PROF_STEPS))
 
     if rank == 0:
-        work_of = {k: v.pop("_work_per_step") for k, v in fam.items()}
-        work = encoder_algorithmic_work(w)
         ms_step = dt / args.steps * 1e3
         frames = w["B"] * w["T"] * world
+        split_on = ops.get_gemm_split() > 0
+        out = {
+            "metric": "audio frames/sec training (LAS+CTC, LibriSpeech 80-mel)",
+            "value": frames / (dt / args.steps), "unit": "frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "dtype_note": ("f32 values everywhere (operands, accumulators, state). Large GEMMs form each f32 product "
+                           "as six exact bf16-MFMA partial products of the exactly split operands (error vs float64 "
+                           "equal to the f32-MFMA kernel's: tests/test_kernels_gpu.py::test_gemm_split_*); "
+                           "ASRK_GEMM_SPLIT=0 runs them on v_mfma_f32_32x32x2_f32") if split_on else "exact f32 MFMA",
+            "gemm_arithmetic": "bf16x6 (exact split)" if split_on else "f32 MFMA",
+            "data": "synthetic", "loss": float(loss.detach()), "grad_norm": float(gn),
+            "config": {"workload": "%s: %s" % (args.workload, json.dumps(
+                {k: w[k] for k in ("B", "T", "D", "V", "L")})), "global_batch": w["B"] * world,
+                "parallelism": "dp%d" % world},
+        }
+        if comm is not None:
+            eng = step.engine
+            # RCCL's own account of the job (torch.distributed "nccl" == RCCL): world size, every rank present once,
+            # and (--full) the part of the gradient all-reduce that was NOT hidden behind the backward pass
+            comm.update({"exposed_allreduce_ms_per_step": eng.exposed_allreduce_ms() if eng is not None else None,
+                         "gradient_bytes": sum(b["numel"] for b in eng._buckets) * 4 if eng is not None else 0,
+                         "buckets": len(eng._buckets) if eng is not None else 0,
+                         "launcher": "bench.py (self-spawned)" if os.environ.get("ASRK_BENCH_SPAWNED") == "1"
+                         else "external (torch.distributed.run)"})
+            out["rccl"] = comm
+    if rank == 0 and args.full:
+        work_of = {k: v.pop("_work_per_step") for k, v in fam.items()}
+        work = encoder_algorithmic_work(w)
         # Dominant kernel by time: the f32-MFMA GEMM (one kernel template, ~45 % of the kernel time of a
         # step; rocprofv3 summary in profiles/).  achieved = algorithmic flops (2*M*N*K of every call,
         # counted by the library while the hipEvent hooks are on) / hipEvent-measured kernel time of the
@@ -792,7 +933,6 @@ def main():
         # if it was collected on THESE kernel sources (kernel_source_digest stamp); a stale summary gives null.
         traffic = rec_traffic = None
         traffic_note = "no HBM-traffic summary under profiles/ for this workload"
-        split_on = ops.get_gemm_split() > 0
         gemm_peak = SPLIT_GEMM_PEAK_TFLOPS if split_on else F32_MFMA_PEAK_TFLOPS
         tpath, tj = newest_traffic_summary(args.workload, kernel_source_digest())
         if tpath and tj is None:
@@ -807,20 +947,7 @@ def main():
                 n = sum(v["launches"] for v in sel)
                 return sum(v["hbm_bytes_per_launch"] * v["launches"] for v in sel) / n if n else None
             traffic, rec_traffic = per_launch("gemm_bf16x6" if split_on else "gemm_f32"), per_launch("lstm_rec_")
-        out = {
-            "metric": "audio frames/sec training (LAS+CTC, LibriSpeech 80-mel)",
-            "value": frames / (dt / args.steps), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "dtype_note": ("f32 values everywhere (operands, accumulators, state). Large GEMMs form each f32 product "
-                           "as six exact bf16-MFMA partial products of the exactly split operands (error vs float64 "
-                           "equal to the f32-MFMA kernel's: tests/test_kernels_gpu.py::test_gemm_split_*); "
-                           "ASRK_GEMM_SPLIT=0 runs them on v_mfma_f32_32x32x2_f32") if split_on else "exact f32 MFMA",
-            "gemm_arithmetic": "bf16x6 (exact split)" if split_on else "f32 MFMA",
-            "data": "synthetic", "loss": float(loss.detach()), "grad_norm": float(gn),
-            "config": {"workload": "%s: %s" % (args.workload, json.dumps(
-                {k: w[k] for k in ("B", "T", "D", "V", "L")})), "global_batch": w["B"] * world,
-                "parallelism": "dp%d" % world},
+        out.update({
             "roofline": {"kernel": ("gemm_bf16x6 (f32 operands split exactly into 3 bf16 planes, 6 bf16-MFMA products "
                                     "per f32 product, f32 accumulate; small / skinny shapes stay on gemm_f32)")
                          if split_on else "gemm_f32 (128x128x32 f32-MFMA tiles + skinny-M streaming variants)",
@@ -866,17 +993,7 @@ def main():
             # recurrence launches served without (hit) / with (miss) a sentinel fill pass, panels taken from the pool
             # (hit), zero-filled anew (miss) or not emitted (skipped: first sight of a shape) over the whole run
             "pools": ops.pool_stats(),
-        }
-        if comm is not None:
-            eng = step.engine
-            # RCCL's own account of the job (torch.distributed "nccl" == RCCL): world size, every rank present once,
-            # and the part of the gradient all-reduce that was NOT hidden behind the backward pass
-            comm.update({"exposed_allreduce_ms_per_step": eng.exposed_allreduce_ms() if eng is not None else None,
-                         "gradient_bytes": sum(b["numel"] for b in eng._buckets) * 4 if eng is not None else 0,
-                         "buckets": len(eng._buckets) if eng is not None else 0,
-                         "launcher": "bench.py (self-spawned)" if os.environ.get("ASRK_BENCH_SPAWNED") == "1"
-                         else "external (torch.distributed.run)"})
-            out["rccl"] = comm
+        })
         if fam["conv_mfma"]["ms_per_step"] > 0:
             # the VGG prenet's implicit-GEMM convolutions (csrc/conv3x3.hip) run on the f32-input matrix cores: their own
             # family, priced against THAT peak (they are not part of `roofline`, whose peak is the bf16x6 one)

@@ -27,7 +27,7 @@ def test_workloads_and_algorithmic_work_match_survey_table():
 
 def test_bench_cli_contract():
     src = open(os.path.join(ROOT, "bench.py")).read()
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in src
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"steps"', '"warmup"', '"ms_per_step"',
                 '"higher_is_better"', '"scaling"', '"vs_baseline"', '"dtype"', '"data"', '"config"',
@@ -71,6 +71,54 @@ def test_bench_refuses_a_world_that_differs_from_gpus_flag():
                            "MASTER_PORT": "29999"})
     assert r.returncode != 0 and not lines
     assert "--gpus 4" in r.stderr
+
+
+def test_bench_refuses_zero_timed_steps():
+    r, lines = _run_bench(["--steps", "0", "--dry-spawn"])
+    assert r.returncode != 0 and not lines
+    assert "--steps" in r.stderr
+
+
+def test_dump_outputs_are_seeded_float_samples_within_the_limit(tmp_path):
+    """--dump-outputs: one .npy per array, float64 kept and everything else float32; an array longer than its cap
+    becomes the same flat sample of its elements in every run, a shorter one is written whole; the whole dump stays
+    within DUMP_LIMIT_BYTES"""
+    import types
+
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    model = torch.nn.Linear(300, 400)
+    out = torch.randn(3, bench.DUMP_CAP, generator=torch.Generator().manual_seed(1))
+    step = types.SimpleNamespace(last={"ctc_output": out, "att_output": None})
+    arrays = bench.training_outputs(model, step, torch.tensor(2.5, requires_grad=True), torch.tensor(4.0))
+    assert sorted(arrays) == ["ctc_output", "grad_norm", "loss", "params"]
+    hyp = types.SimpleNamespace(output_seq=[7, 3], output_scores=[-0.5, -1.25], outIndex=[7, 3])
+    tie = types.SimpleNamespace(output_seq=[3, 7], output_scores=[-1.25, -0.5], outIndex=[3, 7])
+    arrays.update(bench.decode_outputs([[hyp, tie], []]))
+    for name, (a, _) in bench.decode_outputs([[tie, hyp], []]).items():     # hypotheses of equal score, either order
+        assert np.array_equal(a, arrays[name][0], equal_nan=True), name
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    for name, (t, cap) in arrays.items():
+        a, b = (np.load(tmp_path / d / (name + ".npy")) for d in ("a", "b"))
+        assert np.array_equal(a, b, equal_nan=True), name
+        assert a.dtype == (np.float64 if name.startswith("hyp_") else np.float32), name
+        assert a.shape == ((cap,) if np.prod(np.shape(t)) > cap else tuple(np.shape(t))), name
+    s = np.load(tmp_path / "a" / "ctc_output.npy")
+    assert np.isin(s, out.numpy()).all() and not np.array_equal(s, out.numpy().reshape(-1)[:s.size])
+    assert np.array_equal(np.load(tmp_path / "a" / "params.npy"),
+                          torch.cat([model.weight.detach().reshape(-1), model.bias.detach()]).numpy())
+    tok, sc = np.load(tmp_path / "a" / "hyp_tokens.npy"), np.load(tmp_path / "a" / "hyp_token_scores.npy")
+    assert tok.shape == sc.shape == (2, 2, 2)
+    assert tok[0].tolist() == [[3, 7], [7, 3]] and (tok[1] == -1).all()
+    assert sc[0].tolist() == [[-1.25, -0.5], [-0.5, -1.25]] and np.isnan(sc[1]).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    too_big = {"o%d" % i: (torch.zeros(bench.DUMP_CAP), bench.DUMP_CAP)
+               for i in range(bench.DUMP_LIMIT_BYTES // (4 * bench.DUMP_CAP) + 1)}
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "c"), too_big)
+    assert not (tmp_path / "c").exists()
 
 
 def test_stamped_hbm_traffic_of_the_default_workload_describes_these_kernel_sources():

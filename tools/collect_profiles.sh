@@ -11,15 +11,15 @@ cd /tmp && export TMPDIR=/tmp
 for W in cfg2 cfg3; do
   ST=3; [ $W = cfg2 ] && ST=5
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$W -- \
-      python $R/bench.py --workload $W --steps $ST --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats_$W.log 2>&1
+      python $R/bench.py --full --workload $W --steps $ST --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats_$W.log 2>&1
   cp $(find $OUT/stats_$W -name "*kernel_stats.csv" | head -1) $OUT/r01_${W}_kernel_stats.csv
   NL=2; [ $W = cfg3 ] && NL=4
   python $R/tools/step_timeline.py $(find $OUT/stats_$W -name "*kernel_trace.csv" | head -1) 8 $NL \
       > $OUT/r01_${W}_step_timeline.log 2>&1
 done
 cd $R
-python bench.py > $OUT/r01_bench_cfg2.json 2> $OUT/bench_cfg2.err
-python bench.py --workload cfg3 --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/r01_bench_cfg3.json 2> $OUT/bench_cfg3.err
+python bench.py --full > $OUT/r01_bench_cfg2.json 2> $OUT/bench_cfg2.err
+python bench.py --full --workload cfg3 --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/r01_bench_cfg3.json 2> $OUT/bench_cfg3.err
 python tools/gemm_bench.py 2>&1 | grep -v amdgpu.ids > $OUT/r01_gemm_vs_vendor.log
 python tools/skinny_bench.py 2>&1 | grep -v amdgpu.ids >> $OUT/r01_gemm_vs_vendor.log
 (./tools/mfma_peak; ./tools/clock_probe) > $OUT/r01_mfma_peak_clock.log 2>&1

@@ -5,12 +5,12 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-final}
 OUT=$R/gpurun_out/r2_collect_$TAG; mkdir -p $OUT
 cd $R
-python bench.py --steps 20 --warmup 5 > $OUT/r02_bench_cfg3.json 2> $OUT/bench_cfg3.err
-python bench.py --workload cfg2 --steps 40 --warmup 5 > $OUT/r02_bench_cfg2.json 2> $OUT/bench_cfg2.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/r02_bench_cfg3.json 2> $OUT/bench_cfg3.err
+python bench.py --full --workload cfg2 --steps 40 --warmup 5 > $OUT/r02_bench_cfg2.json 2> $OUT/bench_cfg2.err
 python tools/decode_bench.py --cpu-baseline 2> $OUT/decode.err | grep '^{' > $OUT/r02_decode_cfg5.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- \
-    python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats.log 2>&1
+    python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats.log 2>&1
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/r02_cfg3_kernel_stats.csv
 TR=$(find $OUT/stats -name "*kernel_trace.csv" | head -1)
 python $R/tools/step_timeline.py $TR 300 4 > $OUT/r02_cfg3_step_timeline.log 2>&1

@@ -6,7 +6,7 @@ TAG=${1:-a}
 OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- \
-    python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats.log 2>&1
+    python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats.log 2>&1
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 TR=$(find $OUT/stats -name "*kernel_trace.csv" | head -1)
 python $R/tools/step_timeline.py $TR 8 4 > $OUT/step_timeline.log 2>&1

@@ -12,7 +12,7 @@ rm -rf $R/gpurun_out/r4_pmc_hbm_cfg3/FETCH_SIZE $R/gpurun_out/r4_pmc_hbm_cfg3/WR
 cd /tmp && export TMPDIR=/tmp
 for W in cfg3 shipped; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$W -- \
-      python $R/bench.py --workload $W --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats_$W.log 2>&1
+      python $R/bench.py --full --workload $W --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats_$W.log 2>&1
   cp $(find $OUT/stats_$W -name "*kernel_stats.csv" | head -1) $OUT/r04_${W}_kernel_stats.csv
   if [ $W = cfg3 ]; then
     TR=$(find $OUT/stats_$W -name "*kernel_trace.csv" | head -1)
@@ -21,9 +21,9 @@ for W in cfg3 shipped; do
   rm -rf $OUT/stats_$W
 done
 cd $R
-python bench.py --steps 20 --warmup 5 > $OUT/r04_bench_cfg3.json 2> $OUT/bench_cfg3.err
-python bench.py --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r04_bench_cfg2.json 2> $OUT/bench_cfg2.err
-python bench.py --workload shipped --steps 20 --warmup 5 > $OUT/r04_bench_shipped.json 2> $OUT/bench_shipped.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/r04_bench_cfg3.json 2> $OUT/bench_cfg3.err
+python bench.py --full --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r04_bench_cfg2.json 2> $OUT/bench_cfg2.err
+python bench.py --full --workload shipped --steps 20 --warmup 5 > $OUT/r04_bench_shipped.json 2> $OUT/bench_shipped.err
 python tools/solver_bench.py --warmup 45 --steps 30 2> $OUT/solver_bench.err | tail -1 > $OUT/r04_solver_loop_cfg3.json
 python tools/gemm_shapes.py cfg3 2>&1 | grep -v amdgpu.ids > $OUT/r04_gemm_census_cfg3.log
 python tools/rec_timeline.py 800 32 4096 1024 2>&1 | grep -v amdgpu.ids > $OUT/r04_rec_timeline_h1024.log

@@ -14,7 +14,7 @@ done
 cd /tmp && export TMPDIR=/tmp
 for W in cfg3 shipped; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$W -- \
-      python $R/bench.py --workload $W --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats_$W.log 2>&1
+      python $R/bench.py --full --workload $W --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/stats_$W.log 2>&1
   cp $(find $OUT/stats_$W -name "*kernel_stats.csv" | head -1) $OUT/r05_${W}_kernel_stats.csv
   if [ $W = cfg3 ]; then
     TR=$(find $OUT/stats_$W -name "*kernel_trace.csv" | head -1)
@@ -24,11 +24,11 @@ for W in cfg3 shipped; do
   rm -rf $OUT/stats_$W
 done
 cd $R
-python bench.py --steps 20 --warmup 5 > $OUT/r05_bench_cfg3.json 2> $OUT/bench_cfg3.err
-python bench.py --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r05_bench_cfg2.json 2> $OUT/bench_cfg2.err
-python bench.py --workload shipped --steps 20 --warmup 5 > $OUT/r05_bench_shipped.json 2> $OUT/bench_shipped.err
-python bench.py --workload cnn --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r05_bench_cnn.json 2> $OUT/bench_cnn.err
-ASRK_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-exact-check 2> $OUT/bench_dist.err | grep '^{' > $OUT/r05_bench_cfg3_rccl_world1.json
+python bench.py --full --steps 20 --warmup 5 > $OUT/r05_bench_cfg3.json 2> $OUT/bench_cfg3.err
+python bench.py --full --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r05_bench_cfg2.json 2> $OUT/bench_cfg2.err
+python bench.py --full --workload shipped --steps 20 --warmup 5 > $OUT/r05_bench_shipped.json 2> $OUT/bench_shipped.err
+python bench.py --full --workload cnn --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r05_bench_cnn.json 2> $OUT/bench_cnn.err
+ASRK_BENCH_FORCE_DIST=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-exact-check 2> $OUT/bench_dist.err | grep '^{' > $OUT/r05_bench_cfg3_rccl_world1.json
 python tools/solver_bench.py --warmup 45 --steps 30 2> $OUT/solver_bench.err | tail -1 > $OUT/r05_solver_loop_cfg3.json
 python tools/gemm_shapes.py cfg3 2>&1 | grep -v amdgpu.ids > $OUT/r05_gemm_census_cfg3.log
 python tools/rec_timeline.py 800 32 4096 1024 2>&1 | grep -v amdgpu.ids > $OUT/r05_rec_timeline_h1024.log

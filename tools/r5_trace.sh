@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r5}
 OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/p -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/trace_run.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/p -- python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/trace_run.log 2>&1
 f=$(find $OUT/p -name "*kernel_stats.csv" | head -1)
 t=$(find $OUT/p -name "*kernel_trace.csv" | head -1)
 cp "$f" $OUT/kernel_stats.csv

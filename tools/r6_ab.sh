@@ -10,7 +10,7 @@ for E in "$@"; do
   i=$((i+1))
   [ "$E" = "-" ] && E=""
   rm -rf /tmp/p_$i
-  env $E rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$i -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/run_$i.log 2>&1
+  env $E rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p_$i -- python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-exact-check > $OUT/run_$i.log 2>&1
   f=$(find /tmp/p_$i -name "*kernel_stats.csv" | head -1)
   cp "$f" $OUT/kernel_stats_$i.csv
   echo "== [$i] '$E'" >> $OUT/summary.log

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 run() {  # workload env...
   W=$1; shift
-  env "$@" python bench.py --workload $W --steps 10 --warmup 3 --no-cpu-baseline --no-exact-check 2>/dev/null | grep '^{"metric"' | tail -1 | python3 -c "
+  env "$@" python bench.py --full --workload $W --steps 10 --warmup 3 --no-cpu-baseline --no-exact-check 2>/dev/null | grep '^{"metric"' | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); f = d['kernel_families']
 print('  %-6s %-44s ms/step %7.2f  fwd %6.2f  bwd %6.2f' % ('$W', '$*', d['ms_per_step'], f['lstm_fwd']['ms_per_step'], f['lstm_bwd']['ms_per_step']))"

@@ -3,7 +3,7 @@
 # ASRK_GEMM_SPLIT=1: where asrk_gemm_takes_split says it pays (default); 2: wherever the shape allows
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 for W in ${@:-cfg2 shipped}; do for S in 1 2; do
-  ASRK_GEMM_SPLIT=$S python bench.py --workload $W --steps 20 --warmup 5 --no-cpu-baseline --no-exact-check 2>/dev/null | grep '^{' | \
+  ASRK_GEMM_SPLIT=$S python bench.py --full --workload $W --steps 20 --warmup 5 --no-cpu-baseline --no-exact-check 2>/dev/null | grep '^{' | \
     python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); kf = d['kernel_families']
