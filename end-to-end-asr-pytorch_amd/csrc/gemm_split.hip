@@ -27,6 +27,7 @@
 #include "common.h"
 #include "knobs.h"
 #include <algorithm>
+#include <climits>
 
 extern "C" int asrk_cu_count_(void);
 
@@ -46,6 +47,10 @@ struct SplitGemmArgs {
     int nk;                                 // k-tiles
     int tiles_m, tiles_n;
     float alpha, beta;
+    // fixed-order split-K (gemm_bf16x6_kernel<.., SK = true> only): grid = tiles x slices, slice i multiplies the
+    // k-tiles [i nk / slices, (i + 1) nk / slices) and stores its raw accumulators to ws[i][M][ldw]
+    int slices, ldw;
+    float *ws;
 };
 
 // ---------------------------------------------------------------------------------- split pass
@@ -186,10 +191,13 @@ __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F
 // WM = 64-row blocks of A per tile: 2 -> 128x128 tile (4 multiplying + 4 DMA waves), 4 -> 256x128 tile
 // (8 multiplying + 3 DMA waves, two regions each; 72 KiB per stage, 2 stages): a quarter fewer L2 -> LDS bytes
 // per flop, for launches with enough tiles to fill the chip twice.
-template <int NC, int NST, bool SPEC, int WM>
+// SK: split-K.  Block b works on tile b % tiles, slice b / tiles: a contiguous range of k-tiles whose raw accumulators
+// (no alpha, beta, bias) go to the slice's plane of the workspace; splitk_reduce_kernel adds the planes in slice order.
+template <int NC, int NST, bool SPEC, int WM, bool SK = false>
 __global__ __launch_bounds__(SPEC ? (WM == 2 ? 512 : 704) : 256) void gemm_bf16x6_kernel(SplitGemmArgs p) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     static_assert(WM == 2 || (WM == 4 && SPEC), "256-row tiles only with DMA waves");
+    static_assert(!SK || NST >= 2, "the split-K epilogue transposes through a stage the last k-tile does not use");
     constexpr int NPL = 3, CHUNK = NPL * PIECE;   // three bf16 planes
     constexpr int NCW = 2 * WM;                  // multiplying waves (WM x 2, 64x64 each)
     constexpr int NRG = WM + 2;                  // regions per stage: WM row blocks of A, 2 of B
@@ -201,7 +209,11 @@ __global__ __launch_bounds__(SPEC ? (WM == 2 ? 512 : 704) : 256) void gemm_bf16x
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // scalar: LDS-DMA bases stay in SGPRs
     // XCD-aware bijective tile remap (block b runs on XCD b % 8): each XCD walks a contiguous run of tiles,
     // n fastest, so the tiles resident on one XCD share A row blocks and neighbouring B blocks in its L2
-    const int ntiles = p.tiles_m * p.tiles_n, bid = blockIdx.x;
+    const int ntiles = p.tiles_m * p.tiles_n;
+    const int slice = SK ? blockIdx.x / ntiles : 0, bid = SK ? blockIdx.x - slice * ntiles : blockIdx.x;
+    // this block's k-tiles: [kt0, kt0 + nk)
+    const int kt0 = SK ? (int)((long)slice * p.nk / p.slices) : 0;
+    const int nk = SK ? (int)((long)(slice + 1) * p.nk / p.slices) - kt0 : p.nk;
     const int q8 = ntiles >> 3, r8 = ntiles & 7, xcd = bid & 7, loc = bid >> 3;
     const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
     // 8-tile-wide column bands, m fastest inside a band: 32 resident tiles per XCD = 4 x 8 patch
@@ -222,6 +234,7 @@ __global__ __launch_bounds__(SPEC ? (WM == 2 ? 512 : 704) : 256) void gemm_bf16x
         const int r = r0 + q;
         gsrc[q] = (r < WM ? p.Ap + (size_t)(ltm * WM + r) * p.rb_stride_a
                           : p.Bp + (size_t)(ltn * 2 + r - WM) * p.rb_stride_b);          // wave-uniform
+        if (SK) gsrc[q] += (size_t)kt0 * REGION;
     }
     const unsigned voff = lane * 16;
     unsigned char *ldst = lds + r0 * REGION;
@@ -244,7 +257,6 @@ __global__ __launch_bounds__(SPEC ? (WM == 2 ? 512 : 704) : 256) void gemm_bf16x
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int nk = p.nk;
     // fragment addresses: row tile i, plane pl, k-step ks: piece ((ks*2 + h)*3 + pl), row i*32 + (lane&31)
     const int frag_off = ((lane >> 5) * NPL) * PIECE + (lane & 31) * 16;
     const unsigned char *abase = lds + wr * REGION + frag_off;
@@ -357,6 +369,41 @@ __global__ __launch_bounds__(SPEC ? (WM == 2 ? 512 : 704) : 256) void gemm_bf16x
     }
 
     // epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    if constexpr (SK) {
+        // A lane holds four consecutive ROWS of one column: every 32 x 32 accumulator goes through a wave-private LDS
+        // image (row pitch 36 floats) and leaves as 16-byte stores along the workspace rows.  The image lies in the stage
+        // behind the last k-tile's: every wave is past the last barrier, so all reads of the other stages are done and
+        // no LDS-DMA is outstanding (the last tile has landed, nothing was issued after it).
+        constexpr int PITCH = 36;
+        static_assert(NCW * 32 * PITCH * 4 <= STAGE, "transposition images fit one stage");
+        int fstage = stage + 1;
+        if (fstage == NST) fstage = 0;
+        float *img = reinterpret_cast<float *>(lds + fstage * STAGE) + wave * 32 * PITCH;
+        float *wsl = p.ws + (size_t)slice * p.M * p.ldw;
+        const int wrow0 = tm * 64 * WM + wr * 64, wcol0 = tn * 128 + wc * 64;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    img[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * PITCH + (lane & 31)] = acc[i][j][r];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // same-wave LDS hand-over (no barrier needed)
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int idx = q * 64 + lane, rl = idx >> 3, c4 = (idx & 7) * 4;
+                    const f32x4 v = *reinterpret_cast<const f32x4 *>(img + rl * PITCH + c4);
+                    const int row = wrow0 + i * 32 + rl, col = wcol0 + j * 32 + c4;
+                    if (row < p.M && col < p.ldw) *reinterpret_cast<f32x4 *>(wsl + (size_t)row * p.ldw + col) = v;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the next accumulator rewrites the image
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        return;
+    }
     const int row0 = tm * 64 * WM + wr * 64 + 4 * (lane >> 5), col0 = tn * 128 + wc * 64 + (lane & 31);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -376,6 +423,33 @@ __global__ __launch_bounds__(SPEC ? (WM == 2 ? 512 : 704) : 256) void gemm_bf16x
                 if (p.beta != 0.f) v += p.beta * *c;
                 *c = v;
             }
+    }
+}
+
+// Second step of a split-K launch: C = alpha * (ws[0] + ws[1] + ... in slice order) + bias + bias2 + beta * C.  One
+// thread per row and group of four columns; the order of the additions is fixed, so the result is bit-reproducible.
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restrict__ ws, int slices, int M, int N,
+                                                            int ldw, float alpha, float beta, float *__restrict__ C,
+                                                            int ldc, const float *__restrict__ bias,
+                                                            const float *__restrict__ bias2) {
+    const int n4 = ldw >> 2;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)M * n4) return;
+    const int row = (int)(idx / n4), col = (int)(idx - (int64_t)row * n4) * 4;
+    const size_t plane = (size_t)M * ldw;
+    const float *w = ws + (size_t)row * ldw + col;
+    f32x4 a = *reinterpret_cast<const f32x4 *>(w);
+    for (int s = 1; s < slices; ++s) a += *reinterpret_cast<const f32x4 *>(w + (size_t)s * plane);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (col + e >= N) break;
+        float bsum = 0.f;
+        if (bias) bsum += bias[col + e];
+        if (bias2) bsum += bias2[col + e];
+        float *c = C + (size_t)row * ldc + col + e;
+        float v = alpha * a[e] + bsum;
+        if (beta != 0.f) v += beta * *c;
+        *c = v;
     }
 }
 
@@ -604,14 +678,21 @@ int launch_split_gemm_w256(const SplitGemmArgs &a, int rb_b, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------- host side
 // No state here: the panel workspace is the caller's (asrk_gemm_ws_bytes), the split mode is a call flag.
-template <int NC, int NST, bool SPEC, int WM>
+template <int NC, int NST, bool SPEC, int WM, bool SK = false>
 int launch_split_gemm(const SplitGemmArgs &a, hipStream_t s) {
     constexpr int lds = NST * (WM + 2) * NC * 3 * PIECE;
-    auto kern = gemm_bf16x6_kernel<NC, NST, SPEC, WM>;
+    auto kern = gemm_bf16x6_kernel<NC, NST, SPEC, WM, SK>;
     static AsrkLdsLatch latch;
     ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(kern), lds));
-    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n), dim3(SPEC ? (WM == 2 ? 512 : 704) : 256), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n * (SK ? a.slices : 1)), dim3(SPEC ? (WM == 2 ? 512 : 704) : 256),
+                       lds, s, a);
     ASRK_LAUNCH_CHECK();
+    if (SK) {
+        const int64_t items = (int64_t)a.M * (a.ldw >> 2);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)asrk_div_up64(items, 256)), dim3(256), 0, s, a.ws,
+                           a.slices, a.M, a.N, a.ldw, a.alpha, a.beta, a.C, a.ldc, a.bias, a.bias2);
+        ASRK_LAUNCH_CHECK();
+    }
     return ASRK_OK;
 }
 
@@ -658,16 +739,30 @@ int run_split(const float *src, int ld, int rows, int K, bool trans, unsigned ch
     return ASRK_OK;
 }
 
-// C[M,N] = alpha * A_rows * B_rows^T + ...: Ap / Bp point at the first row block and chunk column to use
+// Slice count of a split-K request that leaves the choice to the library (splitk = 0): the smallest one that gives at
+// least one workgroup per CU while every slice keeps at least 64 k-tiles (2048 k: the 128 x 128 kernel's prologue and
+// epilogue stay a few per cent of a slice).  Shapes with N >= 512 fill the chip with tiles, not slices: 1.
+int auto_slices(int M, int N, int nk) {
+    if (N >= 512) return 1;
+    const int ncu = asrk_cu_count_() > 0 ? asrk_cu_count_() : 256;
+    const long tiles = (long)asrk_div_up(M, 128) * asrk_div_up(N, 128);
+    const long want = (ncu + tiles - 1) / tiles;
+    return (int)std::max(1L, std::min(want, (long)(nk / 64)));
+}
+
+// C[M,N] = alpha * A_rows * B_rows^T + ...: Ap / Bp point at the first row block and chunk column to use.
+// slices > 1: fixed-order split-K through `ws` (slices x M x round_up(N, 4) floats), always on the 128 x 128 kernel.
 int run_panel_gemm(int M, int N, int nk, float alpha, const unsigned char *Ap, size_t stride_a,
                    const unsigned char *Bp, size_t stride_b, float beta, float *C, int ldc, const float *bias,
-                   const float *bias2, hipStream_t s) {
+                   const float *bias2, hipStream_t s, int slices = 1, float *ws = nullptr) {
     const AsrkKnobs &kn = asrk_knobs_();
     SplitGemmArgs a;
     a.Ap = Ap; a.Bp = Bp; a.C = C; a.bias = bias; a.bias2 = bias2;
     a.M = M; a.N = N; a.ldc = ldc; a.KC = 0; a.nk = nk; a.rb_stride_a = stride_a; a.rb_stride_b = stride_b;
     a.tiles_m = asrk_div_up(M, 128); a.tiles_n = asrk_div_up(N, 128);
     a.alpha = alpha; a.beta = beta;
+    a.slices = std::min(slices, nk); a.ldw = (N + 3) & ~3; a.ws = ws;
+    if (a.slices > 1) return launch_split_gemm<4, 3, true, 2, true>(a, s);
     // 128 x 256 tiles (gemm_bf16x6_w256_kernel): a quarter fewer LDS bytes per MFMA; needs enough tiles to fill the
     // chip (>= 2 per CU) and at least two 64-row blocks of B per tile row to make the wider tile worth it
     const int w256 = kn.get(kn.split_w256, 1);
@@ -761,10 +856,16 @@ extern "C" int asrk_split_panel_f32(const float *src, int ld, int rows, int K, i
     return rc;
 }
 
-extern "C" int asrk_gemm_panels_f32(int M, int N, int K, float alpha, const void *A_panel, int a_rows, int a_K,
-                                    int a_row0, int a_k0, const void *B_panel, int b_rows, int b_K, int b_row0,
-                                    int b_k0, float beta, float *C, int ldc, const float *bias,
-                                    const float *bias2, int flags, void *stream) {
+namespace {
+// argument checks and operand addresses shared by the two panel-GEMM entry points
+struct PanelRange {
+    const unsigned char *Ap, *Bp;
+    size_t stride_a, stride_b;
+    int nk;
+};
+int panel_range(int M, int N, int K, const void *A_panel, int a_rows, int a_K, int a_row0, int a_k0,
+                const void *B_panel, int b_rows, int b_K, int b_row0, int b_k0, const float *C, int ldc, int flags,
+                PanelRange &r) {
     if (M <= 0 || N <= 0 || K <= 0 || !A_panel || !B_panel || !C || ldc < N || flags != 0) return ASRK_EINVAL;
     if (a_row0 < 0 || b_row0 < 0 || a_k0 < 0 || b_k0 < 0 || a_row0 % 128 || b_row0 % 128 || a_k0 % 8 || b_k0 % 8)
         return ASRK_EINVAL;
@@ -774,16 +875,59 @@ extern "C" int asrk_gemm_panels_f32(int M, int N, int K, float alpha, const void
     if (K % 32 != 0 && a_k0 + K != a_K && b_k0 + K != b_K) return ASRK_ESHAPE;
     const PanelGeom ga = panel_geom(a_rows, a_K, true), gb = panel_geom(b_rows, b_K, true);
     // the k-tiles read must stay inside both panels' padded K
-    const int nk = asrk_div_up(K, 32);
-    if (a_k0 / 8 + nk * SPLIT_NC > ga.KC || b_k0 / 8 + nk * SPLIT_NC > gb.KC) return ASRK_ESHAPE;
+    r.nk = asrk_div_up(K, 32);
+    if (a_k0 / 8 + r.nk * SPLIT_NC > ga.KC || b_k0 / 8 + r.nk * SPLIT_NC > gb.KC) return ASRK_ESHAPE;
+    const unsigned char *A0 = reinterpret_cast<const unsigned char *>(A_panel);
+    const unsigned char *B0 = reinterpret_cast<const unsigned char *>(B_panel);
+    r.Ap = A0 + (size_t)(a_row0 / 64) * ga.rb_stride + (size_t)(a_k0 / 8) * NPL * PIECE;
+    r.Bp = B0 + (size_t)(b_row0 / 64) * gb.rb_stride + (size_t)(b_k0 / 8) * NPL * PIECE;
+    r.stride_a = ga.rb_stride; r.stride_b = gb.rb_stride;
+    return ASRK_OK;
+}
+}  // namespace
+
+extern "C" int asrk_gemm_panels_f32(int M, int N, int K, float alpha, const void *A_panel, int a_rows, int a_K,
+                                    int a_row0, int a_k0, const void *B_panel, int b_rows, int b_K, int b_row0,
+                                    int b_k0, float beta, float *C, int ldc, const float *bias,
+                                    const float *bias2, int flags, void *stream) {
+    PanelRange r;
+    const int rc0 = panel_range(M, N, K, A_panel, a_rows, a_K, a_row0, a_k0, B_panel, b_rows, b_K, b_row0, b_k0, C, ldc,
+                                flags, r);
+    if (rc0 != ASRK_OK) return rc0;
     hipStream_t s = (hipStream_t)stream;
     asrk_prof_work_(PROF_GEMM, 2.0 * (double)M * (double)N * (double)K);
     asrk_prof_begin_(PROF_GEMM, s);
-    const unsigned char *A0 = reinterpret_cast<const unsigned char *>(A_panel);
-    const unsigned char *B0 = reinterpret_cast<const unsigned char *>(B_panel);
-    const unsigned char *Ap = A0 + (size_t)(a_row0 / 64) * ga.rb_stride + (size_t)(a_k0 / 8) * NPL * PIECE;
-    const unsigned char *Bp = B0 + (size_t)(b_row0 / 64) * gb.rb_stride + (size_t)(b_k0 / 8) * NPL * PIECE;
-    const int rc = run_panel_gemm(M, N, nk, alpha, Ap, ga.rb_stride, Bp, gb.rb_stride, beta, C, ldc, bias, bias2, s);
+    const int rc = run_panel_gemm(M, N, r.nk, alpha, r.Ap, r.stride_a, r.Bp, r.stride_b, beta, C, ldc, bias, bias2, s);
+    asrk_prof_end_(PROF_GEMM, s);
+    return rc;
+}
+
+// ---- fixed-order split-K over panels: shapes with few output tiles and a deep K (dW_ih of a narrow-input LSTM layer:
+// 8H x 80 x tokens).  The workspace is the caller's; the library allocates nothing.
+extern "C" size_t asrk_gemm_panels_splitk_ws_bytes(int M, int N, int splitk) {
+    if (M <= 0 || N <= 0 || splitk < 0) return 0;
+    // splitk = 0: the largest count the library's own rule can choose for this output (its K cap only lowers it)
+    const int n = splitk > 0 ? splitk : auto_slices(M, N, INT_MAX);
+    return (size_t)n * (size_t)M * (size_t)((N + 3) & ~3) * sizeof(float);
+}
+
+extern "C" int asrk_gemm_panels_splitk_f32(int M, int N, int K, float alpha, const void *A_panel, int a_rows, int a_K,
+                                           int a_row0, int a_k0, const void *B_panel, int b_rows, int b_K,
+                                           int b_row0, int b_k0, float beta, float *C, int ldc, const float *bias,
+                                           const float *bias2, int splitk, void *ws, size_t ws_bytes, int flags,
+                                           void *stream) {
+    if (splitk < 0 || !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return ASRK_EINVAL;
+    PanelRange r;
+    const int rc0 = panel_range(M, N, K, A_panel, a_rows, a_K, a_row0, a_k0, B_panel, b_rows, b_K, b_row0, b_k0, C, ldc,
+                                flags, r);
+    if (rc0 != ASRK_OK) return rc0;
+    const int slices = splitk > 0 ? splitk : auto_slices(M, N, r.nk);
+    if (ws_bytes < asrk_gemm_panels_splitk_ws_bytes(M, N, slices)) return ASRK_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    asrk_prof_work_(PROF_GEMM, 2.0 * (double)M * (double)N * (double)K);
+    asrk_prof_begin_(PROF_GEMM, s);
+    const int rc = run_panel_gemm(M, N, r.nk, alpha, r.Ap, r.stride_a, r.Bp, r.stride_b, beta, C, ldc, bias, bias2, s,
+                                  slices, reinterpret_cast<float *>(ws));
     asrk_prof_end_(PROF_GEMM, s);
     return rc;
 }

@@ -532,6 +532,8 @@ int rec_bwd_impl(bool gru, float *gates, const float *whh_f, const float *whh_r,
     }
     const bool one_launch = pl.ndir_l >= ndir && pl.nbg_l >= pl.nbg;
     a.rearm = (flags & ASRK_REC_REARM) && one_launch ? 1 : 0;
+    // honoured only where a panel carries dG out of the kernel (the panel entry point; those need the bf16x6 LSTM plan)
+    a.no_dg = (flags & ASRK_REC_BWD_NO_DG) && (dg_panel || dgt_panel) ? 1 : 0;
     if (db) ASRK_HIP(hipMemsetAsync(db, 0, (size_t)ndir * 4 * H * sizeof(float), s));
     asrk_prof_begin_(PROF_LSTM_BWD, s);
     int rc = ASRK_OK;

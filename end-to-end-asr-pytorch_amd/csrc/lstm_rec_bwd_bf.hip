@@ -326,7 +326,8 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
             }
         }
         REC_STAMP(5);
-        if (c_valid) {
+        // f32 dG in place over the gates - unless the caller reads dG from the panels alone (ASRK_REC_BWD_NO_DG)
+        if (c_valid && !p.no_dg) {
             float *g = p.G + ((size_t)t * p.B + c_b) * p.ldg + dir * 4 * H + c_unit;
 #pragma unroll
             for (int r = 0; r < 4; ++r) g[(size_t)r * H] = dgs[r];

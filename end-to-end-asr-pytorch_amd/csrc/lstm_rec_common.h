@@ -58,6 +58,7 @@ struct RecBwdArgs {
     float *db;   // optional [ndir][4H] bias gradient (sum of dG over t and batch), accumulated in-kernel
     int pyr_mode, pyr_rate;   // dY is given in the time-reduced layout of RecFwdArgs::Y2 (0: plain [T*B, ldy])
     int rearm;   // ASRK_REC_REARM (see RecFwdArgs)
+    int no_dg;   // ASRK_REC_BWD_NO_DG: the bf16x6 kernel leaves G as it is (no f32 dG stores); the panels carry dG
     // optional (bf16x6 LSTM kernel only): dG ALSO as the row-major split panel [rows = (t, b)][K = ldg] that the
     // input-gradient GEMM dX = dG W_ih multiplies: the staged 16-byte exchange chunks, once more
     unsigned char *PG;

@@ -91,6 +91,7 @@ def rec_flags(backward):
 
 
 ASRK_REC_REARM = 2            # include/asrk.h: the launch hands the exchange buffer back sentinel-filled
+ASRK_REC_BWD_NO_DG = 4        # include/asrk.h: the BPTT launch stores dG in its panels only, not as f32 over the gates
 _XCHG_REARM = _os.environ.get("ASRK_XCHG_REARM", "1") != "0"
 _XCHG_POOL_CAP = int(float(_os.environ.get("ASRK_XCHG_POOL_GB", "24")) * (1 << 30))
 # free[(device, stream)] = [[buffer, armed_bytes, last_use_tick], ...]; "stats" counts launches served without / with a
@@ -425,6 +426,9 @@ class SplitPanel:
 # splitting its input itself.  ASRK_REC_PANELS=0 turns both off.
 import weakref as _weakref
 _REC_PANELS = _os.environ.get("ASRK_REC_PANELS", "1") != "0"
+# a BPTT launch whose dG is read from its panels alone does not store the f32 dG (LSTMLayerFn.backward, include/asrk.h:
+# ASRK_REC_BWD_NO_DG); False: always store
+_REC_SKIP_DG = True
 # free[(device, stream, rows, K)] = [[buffer, 0, last_use_tick], ...]; "seen" = shapes asked for before
 _panel_pool = {"free": {}, "bytes": 0, "tick": 0, "seen": {}, "stats": {"hit": 0, "miss": 0, "skipped": 0, "evicted": 0}}
 _panel_state = {"hint": False, "handover": None, "stats": {"emitted": 0, "consumed": 0, "dg": 0}}
@@ -492,17 +496,29 @@ def _take_handover(x):
     return None
 
 
-def gemm_panels(M, N, K, A, a_row0, a_k0, B, b_row0, b_k0, C, ldc, alpha=1.0, beta=0.0, bias=None, bias2=None):
-    """C[M,N] = alpha * A[a_row0:+M, a_k0:+K] B[b_row0:+N, b_k0:+K]^T + beta C (+ biases), A / B SplitPanels"""
+def gemm_panels(M, N, K, A, a_row0, a_k0, B, b_row0, b_k0, C, ldc, alpha=1.0, beta=0.0, bias=None, bias2=None,
+                splitk=None):
+    """C[M,N] = alpha * A[a_row0:+M, a_k0:+K] B[b_row0:+N, b_k0:+K]^T + beta C (+ biases), A / B SplitPanels.
+    splitk: None = one workgroup per output tile; n >= 1 = K cut into n slices summed in a fixed order (few tiles, deep
+    K); 0 = the library chooses n"""
     _require_gpu(C)
     avail = C.untyped_storage().nbytes() // C.element_size() - C.storage_offset()
     if ldc < N or avail < (M - 1) * ldc + N:
         raise _lib.AsrkError("gemm_panels: C too small for {}x{} with ld {}".format(M, N, ldc))
     if A.flags != B.flags:
         raise _lib.AsrkError("gemm_panels: the two panels were built in different layouts")
-    _lib.check(_L().asrk_gemm_panels_f32(M, N, K, alpha, _p(A.buf), A.rows, A.K, a_row0, a_k0, _p(B.buf), B.rows,
-                                         B.K, b_row0, b_k0, beta, _p(C), ldc, _p(bias), _p(bias2), A.flags,
-                                         _stream()), "gemm_panels")
+    L = _L()
+    if splitk is None:
+        _lib.check(L.asrk_gemm_panels_f32(M, N, K, alpha, _p(A.buf), A.rows, A.K, a_row0, a_k0, _p(B.buf), B.rows,
+                                          B.K, b_row0, b_k0, beta, _p(C), ldc, _p(bias), _p(bias2), A.flags,
+                                          _stream()), "gemm_panels")
+        return
+    # the slices' partial sums: scratch from torch's caching allocator (stream-ordered, like ops.gemm's panels)
+    nws = int(L.asrk_gemm_panels_splitk_ws_bytes(M, N, splitk))
+    ws = torch.empty((nws,), dtype=torch.uint8, device=C.device)
+    _lib.check(L.asrk_gemm_panels_splitk_f32(M, N, K, alpha, _p(A.buf), A.rows, A.K, a_row0, a_k0, _p(B.buf), B.rows,
+                                             B.K, b_row0, b_k0, beta, _p(C), ldc, _p(bias), _p(bias2), splitk, _p(ws),
+                                             nws, A.flags, _stream()), "gemm_panels")
 
 
 def zeros(shape, device):
@@ -936,12 +952,34 @@ class LSTMLayerFn(Function):
         if bf_bwd and share0 and B % 16 == 0 and not _defer_beside_bptt() and ldg == ndir * 4 * H:
             pGT = _BlankPanel.take(ndir * 4 * H, M, dev)
             _panel_state["stats"]["dgt"] = _panel_state["stats"].get("dgt", 0) + (pGT is not None)
+        w_ih, w_hh = (w_ih_f, w_ih_r), (w_hh_f, w_hh_r)
+        # both directions' dW_ih share one launch only when they are computed on the same stream - and only into
+        # scratch: with a data-parallel engine each direction's GEMM writes its rows straight into that weight's slice
+        # of the gradient bucket (two launches of 4H rows: still >= 2 full rounds of tiles on the wide layers)
+        can_defer = _can_defer(w_ih_f, w_hh_f, w_ih_r, w_hh_r, *ctx.bias_refs)
+        to_scratch = not grad_has_destination(*w_ih[:ndir])
+        stack_dw = (ctx.needs_input_grad[0] or not can_defer) and to_scratch
+        rows_ih = 8 * H if (w_stack is not None and stack_dw) else 4 * H
+        # A NARROW input (cfg3's bottom layer: Din = 80) leaves dW_ih = dG^T X too few output tiles for the split GEMM's
+        # routing rule, yet its K is as deep as the wide layers': it multiplies the dG^T panel too, K cut into slices
+        # that a second kernel sums in a fixed order, one launch over both directions' rows where the result goes to
+        # scratch.  (Until round 6 it ran as exact-f32 GEMMs that read the f32 dG again: 3.4 ms of kernels per cfg3 step.)
+        narrow_ih = pGT is not None and Din % 4 == 0 and not gemm_takes_split(rows_ih, Din, M)
+        if narrow_ih and w_stack is not None and to_scratch:
+            rows_ih = 8 * H
+        # Does anything read the f32 dG?  Not when every weight gradient multiplies dG^T (with pGT every path below runs
+        # param_grads_panels; dW_ih takes panels when Din % 4 == 0), dX is not wanted or multiplies the dG panel, and the
+        # bias gradient was summed in the kernel: then the kernel keeps its four 4-byte stores per cell and step.
+        skip_dg = (_REC_SKIP_DG and pGT is not None and Din % 4 == 0 and (not ctx.needs_input_grad[0] or pG is not None)
+                   and (db_in_kernel or not ctx.has_bias))
         if pG is not None or pGT is not None:
+            _panel_state["stats"]["no_dg"] = _panel_state["stats"].get("no_dg", 0) + skip_dg
             _lib.check(L.asrk_lstm_rec_bwd_pyr_panel_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(C), _p(dYc), T, B, H,
                                                          ndir, _p(xc_.buf), xc_.prefilled, _p(ws),
                                                          _p(db_all if db_in_kernel else None), mode, rate,
                                                          _p(pG.buf if pG is not None else None),
-                                                         _p(pGT.buf if pGT is not None else None), xc_.flags, _stream()),
+                                                         _p(pGT.buf if pGT is not None else None),
+                                                         xc_.flags | (ASRK_REC_BWD_NO_DG if skip_dg else 0), _stream()),
                        "lstm_rec_bwd")
         else:
             _lib.check(L.asrk_lstm_rec_bwd_pyr_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(C), _p(dYc), T, B, H,
@@ -983,9 +1021,10 @@ class LSTMLayerFn(Function):
                 panels[name] = SplitPanel(src, ld, rows, M, True)
             return panels[name]
 
-        def dg_gemm(Mo, No, Ko, m0, k0, pB, b_row0, b_k0, out, ldo):
+        def dg_gemm(Mo, No, Ko, m0, k0, pB, b_row0, b_k0, out, ldo, splitk=None):
             """out[Mo, No] = dG[k0 : k0 + Ko, m0 : m0 + Mo]^T  B-panel rows, through the transposed panel dG^T"""
-            gemm_panels(Mo, No, Ko, panel("dGT", dG, ldg, ndir * 4 * H), m0, k0, pB, b_row0, b_k0, out, ldo)
+            gemm_panels(Mo, No, Ko, panel("dGT", dG, ldg, ndir * 4 * H), m0, k0, pB, b_row0, b_k0, out, ldo,
+                        splitk=splitk)
 
         def param_grads_panels(d):
             pY = panel("YT", Y, ldy, ndir * H)
@@ -993,17 +1032,19 @@ class LSTMLayerFn(Function):
             dw_hh = grad_out(w_hh[d], (4 * H, H), dev)
             # direction 0: dG rows of t >= 1 against Y[t-1]; direction 1: dG rows of t <= T-2 against Y[t+1]
             dg_gemm(4 * H, H, Mh, d * 4 * H, B if d == 0 else 0, pY, d * H, 0 if d == 0 else B, dw_hh, H)
-            rows_ih = 8 * H if (w_stack is not None and stack_dw) else 4 * H
-            if gemm_takes_split(rows_ih, Din, M) and Din % 4 == 0:
+            if (gemm_takes_split(rows_ih, Din, M) or narrow_ih) and Din % 4 == 0:
                 pX = panel("XT", xc, Din, Din)
+                sk = 0 if narrow_ih else None                # narrow: fixed-order split-K, slice count by the library
                 if rows_ih == 8 * H:
                     if dw_ih_stack[0] is None:
                         dw_ih_stack[0] = torch.empty((8 * H, Din), **f32)
-                        dg_gemm(8 * H, Din, M, 0, 0, pX, 0, 0, dw_ih_stack[0], Din)
+                        dg_gemm(8 * H, Din, M, 0, 0, pX, 0, 0, dw_ih_stack[0], Din, sk)
+                        _panel_state["stats"]["dw_ih_splitk"] = _panel_state["stats"].get("dw_ih_splitk", 0) + narrow_ih
                     dw_ih = dw_ih_stack[0][d * 4 * H:(d + 1) * 4 * H]
                 else:
                     dw_ih = grad_out(w_ih[d], (4 * H, Din), dev)
-                    dg_gemm(4 * H, Din, M, d * 4 * H, 0, pX, 0, 0, dw_ih, Din)
+                    dg_gemm(4 * H, Din, M, d * 4 * H, 0, pX, 0, 0, dw_ih, Din, sk)
+                    _panel_state["stats"]["dw_ih_splitk"] = _panel_state["stats"].get("dw_ih_splitk", 0) + narrow_ih
             elif rows_ih == 8 * H:
                 if dw_ih_stack[0] is None:
                     dw_ih_stack[0] = torch.empty((8 * H, Din), **f32)
@@ -1043,30 +1084,25 @@ class LSTMLayerFn(Function):
                 db2 = db.clone()
             return dw_ih, dw_hh, db, db2
 
-        # both directions' dW_ih share one launch only when they are computed on the same stream - and only into
-        # scratch: with a data-parallel engine each direction's GEMM writes its rows straight into that weight's slice
-        # of the gradient bucket (two launches of 4H rows: still >= 2 full rounds of tiles on the wide layers)
-        w_ih, w_hh = (w_ih_f, w_ih_r), (w_hh_f, w_hh_r)
-        stack_dw = ((ctx.needs_input_grad[0] or not _can_defer(w_ih_f, w_hh_f, w_ih_r, w_hh_r, *ctx.bias_refs))
-                    and not grad_has_destination(*w_ih[:ndir]))
         beside = _defer_beside_bptt() or not ctx.needs_input_grad[0]
-        if _can_defer(w_ih_f, w_hh_f, w_ih_r, w_hh_r, *ctx.bias_refs) and beside:
+        if can_defer and beside:
             # off the critical path: the next layer's BPTT does not need dW / db
             if ctx.needs_input_grad[0] or ndir == 1:
                 with _SideStream(dev, (dG, xc, Y, db_all)) as side:
                     share[1] = True
                     grads = [param_grads(d) for d in range(ndir)]
                     side.keep(*[t for g in grads for t in g])
-            elif pGT is not None and gemm_takes_split(4 * H, Din, M) and Din % 4 == 0:
-                # bottom layer with a WIDE input: dW_ih multiplies panels too (X^T) and its GEMMs fill the chip on their
-                # own - stream order, like the layers above
+            elif pGT is not None and Din % 4 == 0:
+                # bottom layer with the dG^T panel from the kernel: every weight gradient multiplies panels (dW_ih with a
+                # wide input like the layers above, with a narrow one through the split-K launch) and fills the chip on
+                # its own - stream order.  (Until round 6 the narrow-input case ran its directions on two streams beside
+                # each other for the sake of the small f32 dW_ih GEMMs; the 256-tile dW_hh launches only serialised there.)
                 share[1] = True
                 grads = [param_grads(d) for d in range(ndir)]
             elif pGT is not None:
-                # bottom layer of a wide stack with the dG^T panel from the kernel: both directions' dW_hh multiply row
-                # ranges of that ONE panel (and of Y^T, split here before the streams fork; dW_ih with a narrow input
-                # takes no panel); the directions still run side by side, the pooled panel goes back at the end of the
-                # backward pass (after the streams re-join)
+                # the same with an input width no panel takes (Din % 4 != 0): dW_hh multiplies row ranges of the ONE dG^T
+                # panel (and of Y^T, split here before the streams fork), dW_ih reads the f32 dG; the directions run side
+                # by side, the pooled panel goes back at the end of the backward pass (after the streams re-join)
                 pY = panel("YT", Y, ldy, ndir * H)
                 share[1] = True
                 with _SideStream(dev, (dG, xc, Y, db_all, pGT.buf, pY.buf), background=False) as side:

@@ -123,6 +123,20 @@ int asrk_gemm_panels_f32(int M, int N, int K, float alpha, const void *A_panel, 
                          int a_row0, int a_k0, const void *B_panel, int b_rows, int b_K, int b_row0, int b_k0,
                          float beta, float *C, int ldc, const float *bias, const float *bias2, int flags,
                          void *stream);
+/* The same product with a fixed-order split-K, for outputs of few 128 x 128 tiles under a deep K (dW_ih = dG^T X of an
+ * LSTM layer with a narrow input, 8H x 80 x tokens: autograd of src/module.py:131; ops.py: LSTMLayerFn.backward,
+ * ops.gemm_panels(splitk=...)).  The k-tiles (32 k) are cut into `splitk` contiguous slices (more slices than k-tiles:
+ * clamped), each slice's raw accumulators go to ws[slice][M][round_up(N, 4)] and a second kernel adds the slices in index
+ * order and applies alpha, beta and the biases: bit-reproducible, no atomics.  splitk = 1 is asrk_gemm_panels_f32's
+ * launch; splitk = 0 lets the library choose (the smallest count with a workgroup per CU while a slice keeps >= 64
+ * k-tiles; 1 for N >= 512).  ws: caller-owned device memory, 16-byte aligned (ASRK_EINVAL if NULL or misaligned), at
+ * least asrk_gemm_panels_splitk_ws_bytes(M, N, splitk) bytes (ASRK_EWORKSPACE otherwise; for splitk = 0 that is the
+ * bound over every K).  ASRK_EINVAL for splitk < 0. */
+size_t asrk_gemm_panels_splitk_ws_bytes(int M, int N, int splitk);
+int asrk_gemm_panels_splitk_f32(int M, int N, int K, float alpha, const void *A_panel, int a_rows, int a_K,
+                                int a_row0, int a_k0, const void *B_panel, int b_rows, int b_K, int b_row0, int b_k0,
+                                float beta, float *C, int ldc, const float *bias, const float *bias2, int splitk,
+                                void *ws, size_t ws_bytes, int flags, void *stream);
 
 /* ---- strided 3-D copy: dst[i0][i1][0:n2] = src[i0][i1][0:n2] (strides in floats) ------
  * Used for [B,T,D]<->[T,B,D] and the pyramid 'concat'/'drop' time reduction
@@ -199,6 +213,11 @@ size_t asrk_lstm_ws_bytes(void);
  * fill behind the kernel covers the last two steps).  A launch that ends in ASRK_ETIMEOUT (asrk_lstm_check_error)
  * leaves the buffer in an undefined state: fill or drop it. */
 #define ASRK_REC_REARM 2
+/* ASRK_REC_BWD_NO_DG (asrk_lstm_rec_bwd_pyr_panel_f32 only; every other entry point ignores it): the BPTT kernel does
+ * NOT store the f32 dG over `gates` - the caller takes dG from the panels alone (dX = dG W_ih from dg_panel, the weight
+ * gradients from dgt_panel, the bias gradient from `db`).  On return `gates` still holds the activated gates.  Saves four
+ * 4-byte stores per cell and step (ops.py: LSTMLayerFn.backward sets it when every consumer of dG takes a panel). */
+#define ASRK_REC_BWD_NO_DG 4
 /* Bytes of the inter-workgroup EXCHANGE buffer a launch needs (fragment-ordered h_t / dG_t of
  * every step; the kernels pre-fill it with a NaN sentinel and poll the data itself). 0 = shape
  * unsupported. backward: 0 for rec_fwd, 1 for rec_bwd. */

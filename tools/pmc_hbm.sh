@@ -8,8 +8,10 @@ W=${1:-cfg2}; NAME=${2:-pmc_hbm_$W}
 OUT=$R/gpurun_out/$NAME; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -- \
-      python $R/bench.py --full --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-exact-check > $OUT/$C.log 2>&1
+  # one pass at a time, each under its own time limit; a pass that fails ends the collection
+  timeout -k 10 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -- \
+      python $R/bench.py --full --workload $W --steps 2 --warmup 1 --no-cpu-baseline --no-exact-check > $OUT/$C.log 2>&1 \
+      || { echo "pmc pass $C failed"; tail -5 $OUT/$C.log; exit 1; }
 done
 python3 - "$OUT" "$W" "$R" <<'PY'
 import csv, sys, glob, collections, json, os

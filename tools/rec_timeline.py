@@ -1,6 +1,6 @@
 """Debug tool (GPU): per-phase timeline of workgroup 0 inside the persistent LSTM kernels.
 
-    python tools/rec_timeline.py [T B D H]
+    python tools/rec_timeline.py [T B D H [passes [skip_dg]]]
 
 phases: 0 step start | 1 exchange fragments loaded sentinel-free | 2 MFMAs done | 3 partials in LDS
         4 past the barrier | 5 cell update done, exchange (sc1) stores issued | 6 saved-tensor
@@ -21,6 +21,13 @@ ops = importlib.import_module(PKG + ".ops")
 lib = importlib.import_module(PKG + "._lib").load()
 
 T, B, D, H = [int(a) for a in sys.argv[1:5]] if len(sys.argv) >= 5 else (1000, 32, 80, 512)
+# passes: forward + backward passes to run; the LAST one is stamped.  A shape's first BPTT launch writes no panels
+# (ops._BlankPanel hands one out from the second request on), so the panel-writing kernel - and with it
+# ASRK_REC_BWD_NO_DG - is seen from passes = 3 on.  skip_dg = 0 keeps the f32 dG stores (ops._REC_SKIP_DG) for a
+# before / after pair.
+PASSES = int(sys.argv[5]) if len(sys.argv) > 5 else 1
+if len(sys.argv) > 6:
+    ops._REC_SKIP_DG = sys.argv[6] != "0"
 dev = "cuda"
 g = torch.Generator().manual_seed(0)
 x = torch.randn(T, B, D, generator=g).to(dev).requires_grad_(True)
@@ -50,6 +57,13 @@ def report(tag, buf, ms):
             w, " ".join("%s %5.0f" % (n, v) for n, v in zip(names, d)), nxt, tot))
 
 
+for _ in range(PASSES - 1):                     # untimed passes: pools, panels
+    ops.lstm_layer(x, pf, pr).backward(torch.randn(T, B, 2 * H, generator=g).to(dev))
+    ops.join_deferred()
+    for q in (x,) + pf + pr:
+        q.grad = None
+torch.cuda.synchronize()
+st0 = dict(ops._panel_state["stats"])
 for tag in ("fwd", "bwd"):
     buf = torch.zeros(STEPS * 4 * 8, dtype=torch.int64, device=dev)
     if tag == "fwd":
@@ -74,4 +88,7 @@ for tag in ("fwd", "bwd"):
         lib.asrk_lstm_set_debug_(None, 0)
         torch.cuda.synchronize()
         report("bwd", buf, ms.value)
+st1 = ops._panel_state["stats"]
+print("stamped BPTT launch: dG panel %d, dG^T panel %d, f32 dG stores skipped %d" % tuple(
+    st1.get(k, 0) - st0.get(k, 0) for k in ("dg", "dgt", "no_dg")))
 ops.check_errors()
