@@ -139,6 +139,11 @@ SIGNATURES = {
     "asrk_conv3x3_wgrad_f32": (c_int, [c_vp] * 5 + [c_int] * 5 + [c_vp, c_sz, c_vp]),
     "asrk_conv3x3_first_supported": (c_int, [c_int] * 4),
     "asrk_conv3x3_first_f32": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_i64] * 4 + [c_int, c_vp]),
+    "asrk_conv3x3_len_f32": (c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp]),
+    "asrk_conv3x3_first_len_f32": (c_int, [c_vp] * 5 + [c_int] * 5 + [c_i64] * 4 + [c_int, c_vp]),
+    "asrk_im2col_ld_len_f32": (c_int, [c_vp] * 3 + [c_int] * 11 + [c_i64] * 4 + [c_vp]),
+    "asrk_im2col_cl_len_f32": (c_int, [c_vp] * 3 + [c_int] * 10 + [c_i64] * 4 + [c_vp]),
+    "asrk_conv_zero_tail_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_vp]),
     "asrk_conv3x3_first_wgrad_ws_bytes": (c_sz, [c_int] * 5),
     "asrk_conv3x3_first_wgrad_f32": (c_int, [c_vp] * 5 + [c_int] * 5 + [c_i64] * 4 + [c_vp, c_sz, c_vp]),
     "asrk_relu_fwd_f32": (c_int, [c_vp, c_i64, c_vp]),

@@ -230,5 +230,65 @@ def conv(x, weight, bias, geom, relu=False):
     return ConvFn.apply(x, weight, bias, geom, relu)
 
 
+def conv_len(x, weight, bias, geom, hlen, relu=False, out_hlen=None):
+    """Inference-only convolution over a padded batch in which image b is hlen[b] <= geom.H rows high: input rows
+    h >= hlen[b] read as exactly zero whatever they hold (the padding a batch-1 run of that image would see), output
+    rows ho >= out_hlen[b] come back as exactly zero.  hlen / out_hlen: [B] int64 DEVICE tensors (read by the kernels,
+    no synchronisation); out_hlen defaults to hlen, which is right for the stride-1 'same' layers and the only thing the
+    3x3 kernels offer.  Same three routes as ConvFn.forward; no autograd node, no backward.  -> [M, Cout]"""
+    _require_gpu(x)
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        raise _lib.AsrkError("conv_len is inference-only")
+    L = _L()
+    xc = _f32c(x.detach())
+    geom.check_extent(xc)
+    w = _f32c(weight.detach())
+    b = _f32c(bias.detach())
+    Cout = w.shape[0]
+    if w.numel() != Cout * geom.K or b.numel() != Cout:
+        raise RuntimeError("conv: weight {} / bias {} do not match Cin*KH*KW = {}".format(
+            tuple(weight.shape), tuple(bias.shape), geom.K))
+    same = (geom.Ho, geom.Wo) == (geom.H, geom.W)
+    if out_hlen is None:
+        if not same:
+            raise _lib.AsrkError("conv_len: out_hlen is required when the convolution changes the height")
+        out_hlen = hlen
+    for t in (hlen, out_hlen):
+        if t.device != xc.device or t.dtype != torch.int64 or t.numel() != geom.B or not t.is_contiguous():
+            raise _lib.AsrkError("conv_len: lengths must be contiguous int64 [B] tensors on the input's device")
+    y = torch.empty((geom.M, Cout), dtype=torch.float32, device=x.device)
+    if out_hlen is hlen and geom.direct3x3_ok(Cout, xc, w, y):
+        wf = torch.empty_like(w)
+        _lib.check(L.asrk_conv3x3_weight_f32(_p(w), _p(wf), Cout, geom.C, 0, _stream()), "conv3x3_weight")
+        _lib.check(L.asrk_conv3x3_len_f32(_p(xc), _p(wf), _p(b), _p(y), _p(hlen), geom.B, geom.H, geom.W, geom.C, Cout,
+                                          int(bool(relu)), _stream()), "conv3x3_len")
+        return y
+    if out_hlen is hlen and geom.first3x3_ok(Cout, w, y):
+        _lib.check(L.asrk_conv3x3_first_len_f32(_p(xc), _p(w), _p(b), _p(y), _p(hlen), geom.B, geom.H, geom.W, geom.C, Cout,
+                                                geom.sb, geom.sh, geom.sw, geom.sc, int(bool(relu)), _stream()),
+                   "conv3x3_first_len")
+        return y
+    Kp = (geom.K + 3) // 4 * 4                      # as ConvFn.forward
+    col = torch.empty((geom.M, Kp), dtype=torch.float32, device=x.device)
+    if geom.channels_last_ok(xc, col):
+        wk = torch.empty_like(w.view(Cout, geom.K))
+        _lib.check(L.asrk_conv_weight_reorder_f32(_p(w), _p(wk), Cout, geom.C, geom.KH * geom.KW, 0, _stream()),
+                   "conv_weight_reorder")
+        _lib.check(L.asrk_im2col_cl_len_f32(_p(xc), _p(col), _p(hlen), *geom.args(), _stream()), "im2col_cl_len")
+    else:
+        if Kp != geom.K:
+            wk = zeros((Cout, Kp), x.device)
+            copy3d(w, wk, 1, Cout, geom.K, 0, geom.K, 0, Kp)
+        else:
+            wk = w
+        _lib.check(L.asrk_im2col_ld_len_f32(_p(xc), _p(col), _p(hlen), Kp, *geom.args(), _stream()), "im2col_len")
+    gemm(0, 1, geom.M, Cout, Kp, col, Kp, wk, Kp, y, Cout, bias=b)
+    if relu:
+        _lib.check(L.asrk_relu_fwd_f32(_p(y), y.numel(), _stream()), "relu")
+    # rows beyond an image's own output extent hold bias (or its ReLU), not zero
+    _lib.check(L.asrk_conv_zero_tail_f32(_p(y), _p(out_hlen), geom.B, geom.Ho, geom.Wo * Cout, _stream()), "conv_zero_tail")
+    return y
+
+
 def maxpool2x2(x, dims, out_shape, ostr):
     return MaxPool2x2Fn.apply(x, dims, out_shape, ostr)

@@ -22,11 +22,22 @@ struct ConvGeom {
     int64_t sb, sh, sw, sc;  // input element strides
 };
 
+// the gathers over a padded batch (inference): image b is min(H, hlen[b]) rows high, the rows beyond read as zero
+struct ConvGeomLen : ConvGeom {
+    const int64_t *hlen;     // [B], device
+};
+
+__device__ __forceinline__ int valid_height(const ConvGeom &g, int) { return g.H; }
+__device__ __forceinline__ int valid_height(const ConvGeomLen &g, int b) {
+    return (int)min((int64_t)g.H, max((int64_t)0, g.hlen[b]));
+}
+
 // col[m, k] = x[b, ho*SH+kh-PH, wo*SW+kw-PW, cin]  (0 outside), m = (b*Ho+ho)*Wo+wo,
 // k = (cin*KH+kh)*KW+kw.  One thread per element, k fastest -> coalesced 4-B stores.  Rows are `ld` >= K floats apart
 // and columns K .. ld-1 are written as zeros (a K that is not a multiple of 4 padded up for the 16-byte GEMM paths).
+template <typename Geom>
 __global__ __launch_bounds__(256) void im2col_kernel(const float *__restrict__ x,
-                                                     float *__restrict__ col, ConvGeom g, int ld,
+                                                     float *__restrict__ col, Geom g, int ld,
                                                      int64_t total) {
     const int KK = g.KH * g.KW;
     const int K = g.C * KK;
@@ -48,7 +59,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float *__restrict__ x
         const int h = ho * g.SH + kh - g.PH;
         const int w = wo * g.SW + kw - g.PW;
         float v = 0.f;
-        if (h >= 0 && h < g.H && w >= 0 && w < g.W)
+        if (h >= 0 && h < valid_height(g, b) && w >= 0 && w < g.W)
             v = x[b * g.sb + h * g.sh + w * g.sw + cin * g.sc];
         col[i] = v;
     }
@@ -198,8 +209,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_vec_kernel(const float *__res
 // three integer divisions (the (cin, kh, kw) kernels above: 1.2 / 1.6 TB/s at the shipped VGG sizes).  The weight is
 // re-ordered to match (Cout x K floats, asrk_conv_weight_reorder_f32) and dW is re-ordered back: both tiny.
 //   col[m, (kh*KW + kw)*C + c] = x[b, ho*SH+kh-PH, wo*SW+kw-PW, c];   grid.y = kh*KW + kw, threads over (m, c/4)
+template <typename Geom>
 __global__ __launch_bounds__(256) void im2col_cl_kernel(const float *__restrict__ x, float *__restrict__ col,
-                                                        ConvGeom g, unsigned total /* M * C/4 */) {
+                                                        Geom g, unsigned total /* M * C/4 */) {
     const int seg = blockIdx.y, kh = seg / g.KW, kw = seg - kh * g.KW;
     const unsigned C4 = (unsigned)g.C >> 2;
     const int64_t K = (int64_t)g.C * g.KH * g.KW;
@@ -209,7 +221,7 @@ __global__ __launch_bounds__(256) void im2col_cl_kernel(const float *__restrict_
         const unsigned b = t / (unsigned)g.Ho, ho = t - b * (unsigned)g.Ho;
         const int h = (int)ho * g.SH + kh - g.PH, w = (int)wo * g.SW + kw - g.PW;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (h >= 0 && h < g.H && w >= 0 && w < g.W)
+        if (h >= 0 && h < valid_height(g, (int)b) && w >= 0 && w < g.W)
             v = *reinterpret_cast<const f32x4 *>(x + (int64_t)b * g.sb + (int64_t)h * g.sh + (int64_t)w * g.sw + c4 * 4);
         *reinterpret_cast<f32x4 *>(col + (int64_t)m * K + (int64_t)seg * g.C + c4 * 4) = v;
     }
@@ -240,6 +252,17 @@ __global__ __launch_bounds__(256) void col2im_cl_kernel(const float *__restrict_
             }
         }
         *reinterpret_cast<f32x4 *>(dx + (int64_t)b * g.sb + (int64_t)h * g.sh + (int64_t)w * g.sw + c4 * 4) = s;
+    }
+}
+
+// y [B, H, row] (contiguous): y[b, h, :] = 0 for h >= hlen[b] - what a convolution over a padded batch leaves beyond an
+// image's own output rows (bias, ReLU of it) is not zero; the length-aware 3x3 kernels write these zeros themselves
+__global__ __launch_bounds__(256) void zero_tail_kernel(float *__restrict__ y, const int64_t *__restrict__ hlen, int H,
+                                                        int64_t row, int64_t total) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t = i / row;
+        const int b = (int)(t / H), h = (int)(t - (int64_t)b * H);
+        if ((int64_t)h >= hlen[b]) y[i] = 0.f;
     }
 }
 
@@ -289,7 +312,25 @@ extern "C" int asrk_im2col_ld_f32(const float *x, float *col, int ldcol, int B, 
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * g.Ho * g.Wo * ldcol;
     asrk_prof_begin_(PROF_CONV, s);
-    hipLaunchKernelGGL(im2col_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, col, g, ldcol, total);
+    hipLaunchKernelGGL(im2col_kernel<ConvGeom>, dim3(grid_for(total)), dim3(256), 0, s, x, col, g, ldcol, total);
+    asrk_prof_end_(PROF_CONV, s);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+extern "C" int asrk_im2col_ld_len_f32(const float *x, float *col, const int64_t *hlen, int ldcol, int B, int H, int W, int C,
+                                      int KH, int KW, int SH, int SW, int PH, int PW, int64_t sb, int64_t sh, int64_t sw,
+                                      int64_t sc, void *stream) {
+    ConvGeomLen g{{B, H, W, C, KH, KW, SH, SW, PH, PW, asrk_conv_out_size(H, KH, SH, PH), asrk_conv_out_size(W, KW, SW, PW),
+                   sb, sh, sw, sc},
+                  hlen};
+    if (!geom_ok(g) || (int64_t)ldcol < (int64_t)C * KH * KW) return ASRK_EINVAL;
+    if (B == 0) return ASRK_OK;
+    if (!x || !col || !hlen) return ASRK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t total = (int64_t)B * g.Ho * g.Wo * ldcol;
+    asrk_prof_begin_(PROF_CONV, s);
+    hipLaunchKernelGGL(im2col_kernel<ConvGeomLen>, dim3(grid_for(total)), dim3(256), 0, s, x, col, g, ldcol, total);
     asrk_prof_end_(PROF_CONV, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
@@ -335,8 +376,41 @@ extern "C" int asrk_im2col_cl_f32(const float *x, float *col, int B, int H, int 
     if (!cl_ok(g, x, col) || total >= (int64_t)1 << 31 || KH * KW > 65535) return ASRK_ESHAPE;
     hipStream_t s = (hipStream_t)stream;
     asrk_prof_begin_(PROF_CONV, s);
-    hipLaunchKernelGGL(im2col_cl_kernel, dim3(std::min(grid_for(total), 16384u), KH * KW), dim3(256), 0, s, x, col, g,
-                       (unsigned)total);
+    hipLaunchKernelGGL(im2col_cl_kernel<ConvGeom>, dim3(std::min(grid_for(total), 16384u), KH * KW), dim3(256), 0, s, x, col,
+                       g, (unsigned)total);
+    asrk_prof_end_(PROF_CONV, s);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+extern "C" int asrk_im2col_cl_len_f32(const float *x, float *col, const int64_t *hlen, int B, int H, int W, int C, int KH,
+                                      int KW, int SH, int SW, int PH, int PW, int64_t sb, int64_t sh, int64_t sw, int64_t sc,
+                                      void *stream) {
+    ConvGeomLen g{{B, H, W, C, KH, KW, SH, SW, PH, PW, asrk_conv_out_size(H, KH, SH, PH), asrk_conv_out_size(W, KW, SW, PW),
+                   sb, sh, sw, sc},
+                  hlen};
+    if (!geom_ok(g)) return ASRK_EINVAL;
+    if (B == 0) return ASRK_OK;
+    if (!x || !col || !hlen) return ASRK_EINVAL;
+    const int64_t total = (int64_t)B * g.Ho * g.Wo * (C / 4);
+    if (!cl_ok(g, x, col) || total >= (int64_t)1 << 31 || KH * KW > 65535) return ASRK_ESHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    asrk_prof_begin_(PROF_CONV, s);
+    hipLaunchKernelGGL(im2col_cl_kernel<ConvGeomLen>, dim3(std::min(grid_for(total), 16384u), KH * KW), dim3(256), 0, s, x,
+                       col, g, (unsigned)total);
+    asrk_prof_end_(PROF_CONV, s);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+extern "C" int asrk_conv_zero_tail_f32(float *y, const int64_t *hlen, int B, int H, int64_t row, void *stream) {
+    if (B < 0 || H <= 0 || row <= 0) return ASRK_EINVAL;
+    if (B == 0) return ASRK_OK;
+    if (!y || !hlen) return ASRK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t total = (int64_t)B * H * row;
+    asrk_prof_begin_(PROF_CONV, s);
+    hipLaunchKernelGGL(zero_tail_kernel, dim3(grid_for(total)), dim3(256), 0, s, y, hlen, H, row, total);
     asrk_prof_end_(PROF_CONV, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;

@@ -24,6 +24,7 @@
 //     the bias gradient (column sums of the masked dy tile) rides along.
 #include "common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -47,8 +48,9 @@ __device__ __forceinline__ f32x4 relu_gate4(f32x4 v, f32x4 gate) {
 }
 
 // halo of rows h0-1 .. h0+TH, columns -1 .. W of channels [c0, c0+64) -> xs[(r*(W+2) + col)*CS + c]
+// rows h >= Hv (<= H: the image's valid height, H itself for the training kernels) read as zero whatever they hold
 __device__ __forceinline__ void stage_halo(float *xs, const float *__restrict__ x, const float *__restrict__ gate,
-                                           int b, int h0, int TH, int H, int W, int C, int c0, int tid) {
+                                           int b, int h0, int TH, int H, int Hv, int W, int C, int c0, int tid) {
     const int W2 = W + 2;
     const int NP = (TH + 2) * W2 * 16;
     constexpr int U = 4;
@@ -61,7 +63,7 @@ __device__ __forceinline__ void stage_halo(float *xs, const float *__restrict__ 
             const int c4 = p & 15, pc = p >> 4;
             const int r = pc / W2, col = pc - r * W2;
             const int h = h0 - 1 + r, w = col - 1;
-            const bool ok = h >= 0 && h < H && w >= 0 && w < W;
+            const bool ok = h >= 0 && h < Hv && w >= 0 && w < W;
             const int hc = min(max(h, 0), H - 1), wc = min(max(w, 0), W - 1);
             const size_t off = (((size_t)b * H + hc) * W + wc) * C + c0 + c4 * 4;
             v[u] = mask4(*reinterpret_cast<const f32x4 *>(x + off), ok);
@@ -85,8 +87,25 @@ struct C3Args {
     int B, H, W, C, tiles_img;    // tiles_img = ceil(H*W / 128)
 };
 
-template <int COUT, bool RELU>
-__global__ __launch_bounds__(256) void conv3x3_kernel(C3Args p) {
+// the length-aware forward (inference over a padded batch): image b is hlen[b] rows high, the rest of its H rows is padding
+struct C3LenArgs : C3Args {
+    const int64_t *hlen;  // [B], device
+};
+
+__device__ __forceinline__ int valid_height(const C3Args &p, int) { return p.H; }
+__device__ __forceinline__ int valid_height(const C3LenArgs &p, int b) {
+    return (int)min((int64_t)p.H, max((int64_t)0, p.hlen[b]));
+}
+
+// y[0 : n4 * 4] = 0 in 16-byte pieces (y 16-byte aligned)
+__device__ __forceinline__ void zero_run(float *y, int n4, int tid) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int i = tid; i < n4; i += 256) reinterpret_cast<f32x4 *>(y)[i] = z;
+}
+
+template <int COUT, bool RELU, typename Args>
+__global__ __launch_bounds__(256) void conv3x3_kernel(Args p) {
+    constexpr bool LEN = std::is_same<Args, C3LenArgs>::value;
     extern __shared__ __attribute__((aligned(16))) float xs[];
     constexpr int NB = COUT / 64;               // 32-column blocks per wave: wave tile 64 rows x COUT/2 columns
     constexpr int NBT = COUT / 32;
@@ -99,6 +118,13 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(C3Args p) {
     const int nvalid = min(128, p.H * W - p0);
     const int h0 = p0 / W, w0 = p0 - h0 * W;
     const int TH = (p0 + nvalid - 1) / W - h0 + 1;            // image rows the tile touches
+    const int Hv = valid_height(p, b);
+    if (LEN && h0 >= Hv) {
+        // the whole tile is padding (uniform over the workgroup, before any barrier): zeros, no staging, no MFMA
+        zero_run(p.y + ((size_t)b * p.H * W + p0) * COUT, nvalid * (COUT / 4), tid);
+        return;
+    }
+    const int mlim = LEN ? Hv * W - p0 : nvalid;              // tile positions below the valid height
 
     int aoff[2];
 #pragma unroll
@@ -120,7 +146,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(C3Args p) {
     const size_t tstride = (size_t)(p.C / 8) * jstride;         // ... between taps
     for (int half = 0; half < nhalf; ++half) {
         if (half) __syncthreads();
-        stage_halo(xs, p.x, p.xmask, b, h0, TH, p.H, W, p.C, half * CH, tid);
+        stage_halo(xs, p.x, p.xmask, b, h0, TH, p.H, Hv, W, p.C, half * CH, tid);
         const f32x4 *bp = reinterpret_cast<const f32x4 *>(p.wf) + (size_t)(half * 8) * jstride + (wn * NB) * 64 + lane;
         f32x4 br[8][NB];
 #pragma unroll
@@ -177,6 +203,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(C3Args p) {
                 if (m < nvalid) {
                     float v = acc[i][n][r] + bv;
                     if (RELU) v = fmaxf(v, 0.f);
+                    if (LEN) v = m < mlim ? v : 0.f;
                     yb[(size_t)m * COUT + col] = v;
                 }
             }
@@ -239,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(W3Args p) {
         const int b = tile / p.tiles_h, h0 = (tile - b * p.tiles_h) * TH;
         const int nvalid = min(TH, p.H - h0) * W;
         __syncthreads();                         // the previous tile's reads are done (and postab is written)
-        stage_halo(xs, p.x, nullptr, b, h0, TH, p.H, W, p.C, cih * CH, tid);
+        stage_halo(xs, p.x, nullptr, b, h0, TH, p.H, p.H, W, p.C, cih * CH, tid);
         const size_t pos0 = ((size_t)b * p.H + h0) * W;
         for (int q0 = tid; q0 < NPD; q0 += 1024) {
             f32x4 v[4], g[4];
@@ -395,23 +422,33 @@ struct F1Args {
     int64_t sb, sh, sw, sc;
 };
 
-// xs[c][(TH+2)][(W+2)]: the halo of every input plane
-__device__ __forceinline__ void stage_planes(float *xs, const F1Args &p, int b, int h0, int tid) {
+struct F1LenArgs : F1Args {
+    const int64_t *hlen;  // [B], device: the valid height of every image (forward only)
+};
+
+__device__ __forceinline__ int valid_height(const F1Args &p, int) { return p.H; }
+__device__ __forceinline__ int valid_height(const F1LenArgs &p, int b) {
+    return (int)min((int64_t)p.H, max((int64_t)0, p.hlen[b]));
+}
+
+// xs[c][(TH+2)][(W+2)]: the halo of every input plane; rows h >= Hv (<= H) read as zero
+__device__ __forceinline__ void stage_planes(float *xs, const F1Args &p, int b, int h0, int Hv, int tid) {
     const int W2 = p.W + 2, R = p.TH + 2;
     const int NP = p.C * R * W2;
     for (int q = tid; q < NP; q += 256) {
         const int c = q / (R * W2), rem = q - c * (R * W2);
         const int r = rem / W2, col = rem - r * W2;
         const int h = h0 - 1 + r, w = col - 1;
-        const bool ok = h >= 0 && h < p.H && w >= 0 && w < p.W;
+        const bool ok = h >= 0 && h < Hv && w >= 0 && w < p.W;
         const int hc = min(max(h, 0), p.H - 1), wc = min(max(w, 0), p.W - 1);
         const float v = p.x[b * p.sb + hc * p.sh + wc * p.sw + c * p.sc];
         xs[q] = __uint_as_float(__float_as_uint(v) & (0u - (unsigned)ok));
     }
 }
 
-template <bool RELU>
-__global__ __launch_bounds__(256) void conv3x3_first_kernel(F1Args p) {
+template <bool RELU, typename Args>
+__global__ __launch_bounds__(256) void conv3x3_first_kernel(Args p) {
+    constexpr bool LEN = std::is_same<Args, F1LenArgs>::value;
     extern __shared__ __attribute__((aligned(16))) float xs[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, kk = lane >> 5;
@@ -419,6 +456,16 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(F1Args p) {
     const int b = blockIdx.x / p.tiles_h, h0 = (blockIdx.x - b * p.tiles_h) * TH;
     const int nvalid = min(TH, p.H - h0) * W;
     const int col = blockIdx.y * 64 + wn * 32 + l31;
+    const int Hv = valid_height(p, b);
+    if (LEN && h0 >= Hv) {
+        // every row of the tile is padding (uniform over the workgroup, before the barrier): this block's 64 columns = 0
+        float *yz = p.y + ((size_t)b * p.H + h0) * W * p.Cout + blockIdx.y * 64;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int i = tid; i < nvalid * 16; i += 256)
+            *reinterpret_cast<f32x4 *>(yz + (size_t)(i >> 4) * p.Cout + (i & 15) * 4) = z;
+        return;
+    }
+    const int mlim = LEN ? (Hv - h0) * W : nvalid;            // tile positions below the valid height
 
     // B fragments: w[col][k], k = 2s + kk (zero beyond K); the matching LDS offsets of A's k
     float bw[16];
@@ -431,7 +478,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(F1Args p) {
         const int c = kc / 9, t = kc - c * 9;
         koff[s] = (c * (TH + 2) + t / 3) * W2 + (t % 3);
     }
-    stage_planes(xs, p, b, h0, tid);
+    stage_planes(xs, p, b, h0, Hv, tid);
     __syncthreads();
     f32x16 acc[2];
 #pragma unroll
@@ -457,6 +504,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(F1Args p) {
             if (m < nvalid) {
                 float v = acc[i][r] + bv;
                 if (RELU) v = fmaxf(v, 0.f);
+                if (LEN) v = m < mlim ? v : 0.f;
                 yb[(size_t)m * p.Cout + col] = v;
             }
         }
@@ -491,7 +539,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_wgrad_kernel(F1Args p) {
         const int b = tile / p.tiles_h, h0 = (tile - b * p.tiles_h) * TH;
         const int nvalid = min(TH, p.H - h0) * W;
         __syncthreads();
-        stage_planes(xs, p, b, h0, tid);
+        stage_planes(xs, p, b, h0, p.H, tid);
         const size_t pos0 = ((size_t)b * p.H + h0) * W;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {                // 128 positions x 16 pieces = 2048 = 2 x 4 x 256
@@ -620,10 +668,10 @@ inline Plan3 wgrad_plan(int B, int H, int W, int splits) {
 
 inline bool al16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
-template <int COUT, bool RELU>
-int launch_conv(const C3Args &a, int lds, hipStream_t s) {
+template <int COUT, bool RELU, typename Args>
+int launch_conv(const Args &a, int lds, hipStream_t s) {
     static AsrkLdsLatch latch;
-    auto kern = conv3x3_kernel<COUT, RELU>;
+    auto kern = conv3x3_kernel<COUT, RELU, Args>;
     ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(kern), 158 * 1024));
     hipLaunchKernelGGL(kern, dim3((unsigned)(a.B * a.tiles_img)), dim3(256), lds, s, a);
     ASRK_LAUNCH_CHECK();
@@ -649,6 +697,19 @@ extern "C" int asrk_conv3x3_weight_f32(const float *w, float *wf, int Cout, int 
     return ASRK_OK;
 }
 
+namespace {
+template <typename Args>
+int conv3x3_dispatch(const Args &a, int Cout, int relu, int lds, hipStream_t s) {
+    asrk_prof_work_(PROF_CONV_MFMA, 2.0 * (double)a.B * a.H * a.W * 9.0 * a.C * Cout);
+    asrk_prof_begin_(PROF_CONV_MFMA, s);
+    int rc;
+    if (Cout == 64) rc = relu ? launch_conv<64, true>(a, lds, s) : launch_conv<64, false>(a, lds, s);
+    else rc = relu ? launch_conv<128, true>(a, lds, s) : launch_conv<128, false>(a, lds, s);
+    asrk_prof_end_(PROF_CONV_MFMA, s);
+    return rc;
+}
+}  // namespace
+
 extern "C" int asrk_conv3x3_f32(const float *x, const float *xmask, const float *wf, const float *bias, float *y, int B,
                                 int H, int W, int C, int Cout, int relu, void *stream) {
     if (B < 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return ASRK_EINVAL;
@@ -658,14 +719,20 @@ extern "C" int asrk_conv3x3_f32(const float *x, const float *xmask, const float 
     if (!asrk_conv3x3_supported(H, W, C, Cout) || !al16(x) || !al16(wf) || (xmask && !al16(xmask))) return ASRK_ESHAPE;
     const Plan3 q = fwd_plan(H, W);
     C3Args a{x, xmask, wf, bias, y, B, H, W, C, q.tiles_h};
-    hipStream_t s = (hipStream_t)stream;
-    asrk_prof_work_(PROF_CONV_MFMA, 2.0 * (double)B * H * W * 9.0 * C * Cout);
-    asrk_prof_begin_(PROF_CONV_MFMA, s);
-    int rc;
-    if (Cout == 64) rc = relu ? launch_conv<64, true>(a, q.lds, s) : launch_conv<64, false>(a, q.lds, s);
-    else rc = relu ? launch_conv<128, true>(a, q.lds, s) : launch_conv<128, false>(a, q.lds, s);
-    asrk_prof_end_(PROF_CONV_MFMA, s);
-    return rc;
+    return conv3x3_dispatch(a, Cout, relu, q.lds, (hipStream_t)stream);
+}
+
+// the forward over a padded batch: image b is min(H, hlen[b]) rows high (hlen: B int64 on the device, read there)
+extern "C" int asrk_conv3x3_len_f32(const float *x, const float *wf, const float *bias, float *y, const int64_t *hlen,
+                                    int B, int H, int W, int C, int Cout, int relu, void *stream) {
+    if (B < 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return ASRK_EINVAL;
+    if (B == 0) return ASRK_OK;
+    if (!x || !wf || !y || !hlen) return ASRK_EINVAL;
+    if (!dims_ok(B, H, W, C, Cout)) return ASRK_ESHAPE;
+    if (!asrk_conv3x3_supported(H, W, C, Cout) || !al16(x) || !al16(wf) || !al16(y)) return ASRK_ESHAPE;
+    const Plan3 q = fwd_plan(H, W);
+    C3LenArgs a{{x, nullptr, wf, bias, y, B, H, W, C, q.tiles_h}, hlen};
+    return conv3x3_dispatch(a, Cout, relu, q.lds, (hipStream_t)stream);
 }
 
 extern "C" size_t asrk_conv3x3_wgrad_ws_bytes(int B, int H, int W, int C, int Cout) {
@@ -739,8 +806,29 @@ extern "C" int asrk_conv3x3_first_f32(const float *x, const float *w, const floa
     hipStream_t s = (hipStream_t)stream;
     asrk_prof_begin_(PROF_CONV, s);
     const dim3 grid((unsigned)(B * q.tiles_h), (unsigned)(Cout / 64));
-    if (relu) hipLaunchKernelGGL(conv3x3_first_kernel<true>, grid, dim3(256), q.lds, s, a);
-    else hipLaunchKernelGGL(conv3x3_first_kernel<false>, grid, dim3(256), q.lds, s, a);
+    if (relu) hipLaunchKernelGGL((conv3x3_first_kernel<true, F1Args>), grid, dim3(256), q.lds, s, a);
+    else hipLaunchKernelGGL((conv3x3_first_kernel<false, F1Args>), grid, dim3(256), q.lds, s, a);
+    asrk_prof_end_(PROF_CONV, s);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+extern "C" int asrk_conv3x3_first_len_f32(const float *x, const float *w, const float *bias, float *y, const int64_t *hlen,
+                                          int B, int H, int W, int C, int Cout, int64_t sb, int64_t sh, int64_t sw,
+                                          int64_t sc, int relu, void *stream) {
+    if (B < 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return ASRK_EINVAL;
+    if (B == 0) return ASRK_OK;
+    if (!x || !w || !y || !hlen) return ASRK_EINVAL;
+    if (!first_ok(B, H, W, C, Cout) || !al16(y)) return ASRK_ESHAPE;
+    const Plan3 q = first_plan(H, W, C, false);
+    F1LenArgs a{{x, w, bias, y, nullptr, nullptr, nullptr, nullptr, B, H, W, C, Cout, q.TH, q.tiles_h, B * q.tiles_h, sb, sh, sw,
+                 sc},
+                hlen};
+    hipStream_t s = (hipStream_t)stream;
+    asrk_prof_begin_(PROF_CONV, s);
+    const dim3 grid((unsigned)(B * q.tiles_h), (unsigned)(Cout / 64));
+    if (relu) hipLaunchKernelGGL((conv3x3_first_kernel<true, F1LenArgs>), grid, dim3(256), q.lds, s, a);
+    else hipLaunchKernelGGL((conv3x3_first_kernel<false, F1LenArgs>), grid, dim3(256), q.lds, s, a);
     asrk_prof_end_(PROF_CONV, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;

@@ -579,20 +579,28 @@ class Encoder(nn.Module):
         self.layers = nn.ModuleList(module_list)
 
     def supports_packed(self):
-        ''' forward(packed=True) is available: no prenet (its convolutions would see the neighbours' padding) and
-            every recurrent layer is an LSTM with a hidden size the packed kernel takes '''
-        return not (self.vgg or self.cnn) and all(l.supports_packed() for l in self.layers)
+        ''' forward(packed=True) is available: every recurrent layer is an LSTM with a hidden size the packed kernel
+            takes (GRU layers: no length-aware recurrence yet).  A VGG / CNN prenet does not stand in the way: its
+            packed form gives every convolution a per-utterance valid height (forward_bm2tm(packed=True)) '''
+        return all(l.supports_packed() for l in self.layers if isinstance(l, RNNLayer))
 
     def forward(self, input_x, enc_len, packed=False):
         ''' packed=True (inference): input_x [U,T,D] zero-padded, enc_len [U]; every utterance is encoded exactly as
-            if it had been passed alone and unpadded (RNNLayer.forward_tm(packed=True)); output frames beyond an
+            if it had been passed alone and unpadded (the prenet's forward_bm2tm(packed=True), then
+            RNNLayer.forward_tm(packed=True)); a prenet never reads input frames beyond enc_len; output frames beyond an
             utterance's length are zero (LayerNorm / projection outputs there are NOT - consumers mask by length) '''
         if packed:
             if not self.supports_packed():
                 raise RuntimeError('Encoder: packed encoding is not available for this configuration')
-            x = ops.swap_bt(input_x)
+            layers = list(self.layers)
+            if self.vgg or self.cnn:
+                # a batch-1 prenet run emits exactly the frames it reports (L // 4): frames == enc_len behind it
+                x, enc_len = layers[0].forward_bm2tm(input_x, enc_len, packed=True)
+                layers = layers[1:]
+            else:
+                x = ops.swap_bt(input_x)
             frames = enc_len
-            for layer in self.layers:
+            for layer in layers:
                 x, enc_len, frames = layer.forward_tm(x, enc_len, packed=True, frames=frames)
             # frames an utterance's own (batch-1) encoder output would have: what everything that walks the output
             # TENSOR of such a run sees (CTC prefix scorer, CTC beam search); == enc_len unless a 'drop' reduction

@@ -133,12 +133,16 @@ class VGGExtractor(nn.Module):
             raise ValueError('Acoustic feature dimension for VGG should be 13/26/39(MFCC) or '
                              '40/80/120(Fbank) but got ' + str(input_dim))
 
-    def forward_bm2tm(self, feature, feat_len):
+    def forward_bm2tm(self, feature, feat_len, packed=False):
         ''' [B,T,C*F] batch-major -> ([T//4, B, 128*(F//4)] time-major, feat_len//4).
         view_input's crop (t % 4) and [B,T,C,F]->[B,C,T,F] transpose (src/module.py:44-57) are
         folded into the first im2col's strides; the final [B,128,T/4,F/4]->[B,T/4,128*F/4]
-        transpose (62-65) and the batch/time swap into the last pool's output strides. '''
+        transpose (62-65) and the batch/time swap into the last pool's output strides.
+        packed (inference): row u is an utterance of feat_len[u] frames and comes out exactly as this prenet run on
+        feature[u:u+1, :feat_len[u]] alone; output frames >= feat_len[u] // 4 are zero (_forward_packed). '''
         from .. import conv_ops as C
+        if packed:
+            return self._forward_packed(feature, feat_len)
         feat_len = feat_len // 4
         bs, ts, ds = feature.shape
         Cin, Fq = self.in_channel, self.freq_dim
@@ -161,6 +165,38 @@ class VGGExtractor(nn.Module):
         h = C.maxpool2x2(h, (bs, T2, F2, 128), (T4, bs, 128 * F4), (128 * F4, bs * 128 * F4, 1, F4))
         return h, feat_len
 
+    def _forward_packed(self, feature, feat_len):
+        ''' A batch-1 run of utterance u crops it to T_u = L_u - L_u % 4 frames (view_input, src/module.py:44-57) and
+        every 3x3 convolution pads with zeros at time row T_u (T_u / 2 behind the first pool).  In the padded batch the
+        rows beyond T_u hold the cropped frames, the neighbours' padding or, from the second layer on, relu(bias + ...);
+        the length-aware convolutions (conv_ops.conv_len) read every input row >= hlen[u] as zero and write every
+        output row >= hlen[u] as zero.  T_u is a multiple of 4, so no pooling window straddles an utterance's last row
+        and the pools stay as they are; the utterance gets T_u / 4 = L_u // 4 frames, its reported length. '''
+        from .. import conv_ops as C
+        bs, ts, ds = feature.shape
+        Cin, Fq = self.in_channel, self.freq_dim
+        T = ts - ts % 4
+        if T < 4:
+            raise RuntimeError('VGG prenet needs at least 4 frames, got {}'.format(ts))
+        lens = torch.as_tensor(feat_len).to(device=feature.device, dtype=torch.int64)
+        out_len = feat_len // 4
+        h1 = ((lens // 4) * 4).clamp(0, T).contiguous()          # valid time rows of the first two layers
+        h2 = (h1 // 2).contiguous()                              # ... of the last two
+        ex = self.extractor
+        g = C.Geom(bs, T, Fq, Cin, 3, 3, 1, 1, 1, 1, ts * ds, ds, 1, Fq)
+        h = C.conv_len(feature, ex[0].weight, ex[0].bias, g, h1, relu=True)
+        g = C.Geom(bs, T, Fq, 64, 3, 3, 1, 1, 1, 1, T * Fq * 64, Fq * 64, 64, 1)
+        h = C.conv_len(h, ex[2].weight, ex[2].bias, g, h1, relu=True)
+        T2, F2 = T // 2, Fq // 2
+        h = C.maxpool2x2(h, (bs, T, Fq, 64), (bs * T2 * F2, 64), (T2 * F2 * 64, F2 * 64, 64, 1))
+        g = C.Geom(bs, T2, F2, 64, 3, 3, 1, 1, 1, 1, T2 * F2 * 64, F2 * 64, 64, 1)
+        h = C.conv_len(h, ex[5].weight, ex[5].bias, g, h2, relu=True)
+        g = C.Geom(bs, T2, F2, 128, 3, 3, 1, 1, 1, 1, T2 * F2 * 128, F2 * 128, 128, 1)
+        h = C.conv_len(h, ex[7].weight, ex[7].bias, g, h2, relu=True)
+        T4, F4 = T2 // 2, F2 // 2
+        h = C.maxpool2x2(h, (bs, T2, F2, 128), (T4, bs, 128 * F4), (128 * F4, bs * 128 * F4, 1, F4))
+        return h, out_len
+
     def forward(self, feature, feat_len):
         ''' reference API: BSxTxD -> BSxT/4x(128*D/4) '''
         out, feat_len = self.forward_bm2tm(feature, feat_len)
@@ -180,10 +216,14 @@ class CNNExtractor(nn.Module):
             nn.Conv1d(out_dim, out_dim, 4, stride=2, padding=1),
         )
 
-    def forward_bm2tm(self, feature, feat_len):
+    def forward_bm2tm(self, feature, feat_len, packed=False):
         ''' [B,T,D] batch-major -> ([T', B, out_dim] time-major, feat_len//4).  The "width" axis
-        of the convolution geometry is the batch, so GEMM rows come out ordered (t', b). '''
+        of the convolution geometry is the batch, so GEMM rows come out ordered (t', b).
+        packed (inference): row u is an utterance of feat_len[u] frames and comes out as this prenet run on
+        feature[u:u+1, :feat_len[u]] alone; output frames >= feat_len[u] // 4 are zero (_forward_packed). '''
         from .. import conv_ops as C
+        if packed:
+            return self._forward_packed(feature, feat_len)
         feat_len = feat_len // 4
         bs, ts, ds = feature.shape
         ex = self.extractor
@@ -193,6 +233,29 @@ class CNNExtractor(nn.Module):
         g = C.Geom(1, T1, bs, O, 4, 1, 2, 1, 1, 0, 0, bs * O, O, 1)
         h = C.conv(h, ex[1].weight, ex[1].bias, g)
         return h.view(g.Ho, bs, O), feat_len
+
+    def _forward_packed(self, feature, feat_len):
+        ''' A batch-1 run of an utterance of L frames pads each Conv1d(k=4, stride 2, pad 1) with one zero frame at
+        either end: L // 2 frames after the first, L // 4 after the second.  A per-utterance length needs the
+        UTTERANCE as the image of the convolution geometry (height = time, width 1), not the batch as its width as in
+        forward_bm2tm; the first layer then reads frames >= L as zero (whatever the caller padded with), the second
+        reads rows >= L // 2 - the first layer's bias in the padded batch - as zero, and rows >= L // 4 of the result
+        are cleared.  Rows come out ordered (u, t'): one swap to time-major. '''
+        from .. import conv_ops as C
+        bs, ts, ds = feature.shape
+        O = self.out_dim
+        lens = torch.as_tensor(feat_len).to(device=feature.device, dtype=torch.int64)
+        out_len = feat_len // 4
+        l0 = lens.clamp(0, ts).contiguous()
+        l1 = (l0 // 2).contiguous()
+        l2 = (l1 // 2).contiguous()
+        ex = self.extractor
+        g = C.Geom(bs, ts, 1, ds, 4, 1, 2, 1, 1, 0, ts * ds, ds, 0, 1)             # reads [B,T,D] in place
+        h = C.conv_len(feature, ex[0].weight, ex[0].bias, g, l0, out_hlen=l1)     # [B*T1, out]
+        T1 = g.Ho
+        g = C.Geom(bs, T1, 1, O, 4, 1, 2, 1, 1, 0, T1 * O, O, 0, 1)
+        h = C.conv_len(h, ex[1].weight, ex[1].bias, g, l1, out_hlen=l2)           # [B*T2, out]
+        return ops.swap_bt(h.view(bs, g.Ho, O)), out_len
 
     def forward(self, feature, feat_len):
         out, feat_len = self.forward_bm2tm(feature, feat_len)

@@ -620,6 +620,32 @@ size_t asrk_conv3x3_first_wgrad_ws_bytes(int B, int H, int W, int C, int Cout);
 int asrk_conv3x3_first_wgrad_f32(const float *x, const float *dy, const float *ymask, float *dw, float *db, int B, int H,
                                  int W, int C, int Cout, int64_t sb, int64_t sh, int64_t sw, int64_t sc, void *ws,
                                  size_t ws_bytes, void *stream);
+/* Length-aware FORWARD entries (inference over a zero- or garbage-padded batch: several utterances encoded together,
+ * each as if it were alone).  hlen: B int64 values on the DEVICE (the convention of asrk_lstm_rec_fwd_len_f32's `lens`),
+ * read by the kernels - no host synchronisation.  Image b is Hv = min(H, max(0, hlen[b])) rows high:
+ *   - an input element (b, h, w) counts only if 0 <= h < Hv; every other one reads as exactly 0 (a select - the rows
+ *     beyond Hv may hold anything, NaN included), so the row h = Hv is the zero padding a batch-1 run of that image sees;
+ *   - asrk_conv3x3_len_f32 / asrk_conv3x3_first_len_f32 (same shapes, layouts and support predicates as
+ *     asrk_conv3x3_f32 without xmask / asrk_conv3x3_first_f32; y 16-byte aligned) write output rows h >= Hv as exactly 0
+ *     (no bias, no ReLU of it), and a workgroup whose whole tile lies there writes its zeros without staging its halo or
+ *     issuing an MFMA: the padded tail of a batch costs a store.  Every valid output element is summed in the order of
+ *     the plain entries, which depends on neither the tile position nor B: bit-identical to the batch-1 result;
+ *   - asrk_im2col_ld_len_f32 / asrk_im2col_cl_len_f32 (arguments of asrk_im2col_ld_f32 / asrk_im2col_cl_f32 plus hlen)
+ *     gather with the same select; patch rows whose output row lies beyond the image's own output extent are whatever
+ *     that yields (bias after the GEMM) - asrk_conv_zero_tail_f32 clears them;
+ *   - asrk_conv_zero_tail_f32: y [B, H, row] contiguous, y[b, h, :] = 0 for h >= hlen[b].
+ * ASRK_EINVAL for a NULL hlen or any other NULL pointer, ASRK_ESHAPE as the plain entries.  No backward. */
+int asrk_conv3x3_len_f32(const float *x, const float *wf, const float *bias, float *y, const int64_t *hlen, int B, int H,
+                         int W, int C, int Cout, int relu, void *stream);
+int asrk_conv3x3_first_len_f32(const float *x, const float *w, const float *bias, float *y, const int64_t *hlen, int B, int H,
+                               int W, int C, int Cout, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int relu,
+                               void *stream);
+int asrk_im2col_ld_len_f32(const float *x, float *col, const int64_t *hlen, int ldcol, int B, int H, int W, int C, int KH,
+                           int KW, int SH, int SW, int PH, int PW, int64_t sb, int64_t sh, int64_t sw, int64_t sc,
+                           void *stream);
+int asrk_im2col_cl_len_f32(const float *x, float *col, const int64_t *hlen, int B, int H, int W, int C, int KH, int KW,
+                           int SH, int SW, int PH, int PW, int64_t sb, int64_t sh, int64_t sw, int64_t sc, void *stream);
+int asrk_conv_zero_tail_f32(float *y, const int64_t *hlen, int B, int H, int64_t row, void *stream);
 int asrk_relu_fwd_f32(float *x, int64_t n, void *stream);
 int asrk_relu_bwd_f32(const float *y, const float *dy, float *dx, int64_t n, void *stream);
 int asrk_maxpool2x2_fwd_f32(const float *x, float *y, uint8_t *idx, int B, int H, int W, int C,
