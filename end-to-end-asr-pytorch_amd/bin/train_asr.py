@@ -13,6 +13,7 @@ from ..src.solver import BaseSolver
 from ..src.asr import ASR
 from ..src.optim import Optimizer
 from ..src.data import load_dataset
+from ..src.audio import SpecAugment
 from ..src.util import human_format, cal_er
 
 
@@ -46,6 +47,11 @@ class Solver(BaseSolver):
             load_dataset(self.paras.njobs, self.paras.gpu, self.paras.pin_memory,
                          self.curriculum > 0, **self.config['data'])
         self.verbose(msg)
+        # training-time input augmentation (top-level `specaug:` block; None = the step is exactly what it was)
+        audio = self.config['data']['audio']
+        self.specaug = SpecAugment.from_config(self.config, audio['feat_dim'], audio.get('delta_order', 0) + 1)
+        if self.specaug is not None:
+            self.verbose(self.specaug.create_msg())
 
     def set_model(self):
         ''' Setup ASR model and optimizer '''
@@ -106,6 +112,10 @@ class Solver(BaseSolver):
                 # Pre-step : update tf_rate/lr_rate and do zero_grad
                 tf_rate = self.optimizer.pre_step(self.step)
                 feat, feat_len, txt, txt_len = self.fetch_data(data)
+                if self.specaug is not None:
+                    # keyed by (seed, step, rank): a resumed run continues the same stream; data[2] = the lengths
+                    # on the host, as the collate function made them (no read-back)
+                    feat = self.specaug(feat, data[2], self.paras.seed, self.step, self.rank, feat_len_dev=feat_len)
                 self.timer.cnt('rd')
 
                 # Note: txt should NOT start w/ <sos>

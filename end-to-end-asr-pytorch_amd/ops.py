@@ -1434,3 +1434,28 @@ def dropout(x, p, training, seed=None):
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     return DropoutFn.apply(x, p, seed)
+
+
+def spec_augment(x, lens, params, n_fmask, n_tmask, fill=0.0, channels=1):
+    """SpecAugment of a padded feature batch in one launch (csrc/spec_augment.hip; semantics: include/asrk.h
+    asrk_spec_augment_f32).  x [B, T, channels * D] f32 on the GPU; lens [B] int64 and params
+    [B, 2 + 2*n_fmask + 2*n_tmask] int32 (rows c, w, f0_0, fw_0, .., t0_0, tw_0, ..), both on x's device.  Returns a new
+    tensor of x's shape.  No autograd: an augmentation of the INPUT, applied under no_grad."""
+    _require_gpu(x)
+    xc = _f32c(x.detach())
+    if xc.dim() != 3:
+        raise ValueError("spec_augment expects [B, T, F] features, got %s" % (tuple(xc.shape),))
+    B, T, F = xc.shape
+    P = 2 + 2 * int(n_fmask) + 2 * int(n_tmask)
+    if channels <= 0 or F % channels != 0:
+        raise ValueError("feature width %d is no multiple of %d channels" % (F, channels))
+    if (lens.dtype != torch.int64 or lens.device != xc.device or tuple(lens.shape) != (B,)
+            or not lens.is_contiguous()):
+        raise ValueError("lens must be a contiguous int64 [B] tensor on x's device")
+    if (params.dtype != torch.int32 or params.device != xc.device or tuple(params.shape) != (B, P)
+            or not params.is_contiguous()):
+        raise ValueError("params must be a contiguous int32 [B, %d] tensor on x's device" % P)
+    y = torch.empty_like(xc)
+    _lib.check(_L().asrk_spec_augment_f32(_p(xc), _p(y), B, T, F, F // channels, channels, _p(lens), _p(params),
+                                          int(n_fmask), int(n_tmask), float(fill), _stream()), "spec_augment")
+    return y

@@ -482,6 +482,136 @@ class BatchFeatureTransform:
         return out, feat_len
 
 
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+class SpecAugment:
+    """SpecAugment (Park et al. 2019: time warp, frequency masks, time masks) for a padded training batch that is
+    already in HBM.  The policy is sampled on the HOST into one int32 row per utterance, as a pure function of
+    (lens, seed, step, rank); the device side is one launch (ops.spec_augment -> csrc/spec_augment.hip, semantics in
+    include/asrk.h).  Resuming from a checkpoint at step s therefore continues the same stream of masks: nothing of it
+    is state.
+
+    Row layout, P = 2 + 2*n_freq_mask + 2*n_time_mask: c, w, f0_0, fw_0, .., t0_0, tw_0, ..  For an utterance of n
+    frames, D = feat_dim mel bins, W = time_warp:
+      * n >= 2W + 2 and W >= 2: c ~ U{W..n-1-W} (the frame that moves), w ~ U{-(W-1)..W-1} (by how much); else c = w = 0;
+      * fw ~ U{0..min(freq_mask_width, D)}, f0 ~ U{0..D-fw};
+      * tw ~ U{0..min(time_mask_width, floor(time_mask_ratio * n))}, t0 ~ U{0..n-tw}."""
+
+    KEYS = ('freq_mask_width', 'n_freq_mask', 'time_mask_width', 'n_time_mask', 'time_mask_ratio', 'time_warp',
+            'mask_value')
+    MAX_MASKS = 8           # SA_MAX_MASKS of csrc/spec_augment.hip
+
+    def __init__(self, feat_dim, channels, freq_mask_width=27, n_freq_mask=2, time_mask_width=100, n_time_mask=2,
+                 time_mask_ratio=1.0, time_warp=80, mask_value=0.0):
+        ints = dict(feat_dim=feat_dim, channels=channels, freq_mask_width=freq_mask_width, n_freq_mask=n_freq_mask,
+                    time_mask_width=time_mask_width, n_time_mask=n_time_mask, time_warp=time_warp)
+        for k, v in ints.items():
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError('specaug: %s must be a non-negative integer, got %r' % (k, v))
+        if feat_dim < 1 or channels < 1:
+            raise ValueError('specaug: feat_dim and channels must be positive')
+        if n_freq_mask > self.MAX_MASKS or n_time_mask > self.MAX_MASKS:
+            raise ValueError('specaug: at most %d masks of each kind' % self.MAX_MASKS)
+        if isinstance(time_mask_ratio, bool) or not isinstance(time_mask_ratio, (int, float)) or \
+                not 0.0 <= time_mask_ratio < float('inf'):
+            raise ValueError('specaug: time_mask_ratio must be a non-negative number, got %r' % (time_mask_ratio,))
+        if isinstance(mask_value, bool) or not isinstance(mask_value, (int, float)) or not math.isfinite(mask_value):
+            raise ValueError('specaug: mask_value must be a finite number, got %r' % (mask_value,))
+        self.feat_dim, self.channels = feat_dim, channels
+        self.freq_mask_width, self.n_freq_mask = freq_mask_width, n_freq_mask
+        self.time_mask_width, self.n_time_mask = time_mask_width, n_time_mask
+        self.time_mask_ratio, self.time_warp, self.mask_value = float(time_mask_ratio), time_warp, float(mask_value)
+        self.P = 2 + 2 * n_freq_mask + 2 * n_time_mask
+
+    @classmethod
+    def from_config(cls, cfg, feat_dim, channels):
+        """cfg: the whole yaml config (a mapping); its top-level `specaug:` block holds `enable` and the constructor's
+        keys.  -> None when the block is absent or `enable: false`."""
+        block = cfg.get('specaug') if cfg is not None else None
+        if block is None:
+            return None
+        if not isinstance(block, dict):
+            raise ValueError('specaug: expected a mapping, got %r' % (block,))
+        block = dict(block)
+        enable = block.pop('enable', True)
+        if not isinstance(enable, bool):
+            raise ValueError('specaug: enable must be true or false, got %r' % (enable,))
+        unknown = sorted(set(block) - set(cls.KEYS))
+        if unknown:
+            raise ValueError('specaug: unknown key(s) %s (known: enable, %s)' % (unknown, ', '.join(cls.KEYS)))
+        policy = cls(feat_dim, channels, **block)        # a disabled block is still checked
+        return policy if enable else None
+
+    @staticmethod
+    def stream_seed(seed, step, rank=0):
+        """the generator seed of one (run seed, data-parallel rank, training step)"""
+        z = 0
+        for v in (seed, rank, step):
+            z = _splitmix64(z ^ (int(v) & _M64))
+        return z & 0x7fffffffffffffff
+
+    def sample(self, lens, seed, step, rank=0):
+        """lens: the utterances' frame counts ON THE HOST (list / numpy / CPU tensor) -> int32 [B, P] (CPU)"""
+        if torch.is_tensor(lens):
+            if lens.is_cuda:
+                raise ValueError('SpecAugment.sample takes the lengths on the host (reading them back would stall the '
+                                 'step)')
+            lens = lens.numpy()
+        n = np.maximum(np.asarray(lens, dtype=np.int64).reshape(-1), 0)
+        B, D, W, nf = n.shape[0], self.feat_dim, self.time_warp, self.n_freq_mask
+        g = torch.Generator()
+        g.manual_seed(self.stream_seed(seed, step, rank))
+        # one uniform per table entry, drawn whether the entry is used or not: an entry's value never depends on
+        # which of the other entries were active.  U{0..count-1} = min(floor(u * count), count - 1) in float64.
+        # (numpy from here on: the table is a few dozen numbers and this runs on the host inside the training step)
+        u = torch.rand((B, self.P), generator=g, dtype=torch.float64).numpy()
+        fw_cols, tw_cols = np.arange(3, 2 + 2 * nf, 2), np.arange(3 + 2 * nf, self.P, 2)
+        count = np.ones((B, self.P), dtype=np.int64)
+        count[:, 0], count[:, 1] = np.maximum(n - 2 * W, 1), max(2 * W - 1, 1)
+        count[:, fw_cols] = min(self.freq_mask_width, D) + 1
+        cap = np.minimum(np.floor(n * self.time_mask_ratio).astype(np.int64), np.minimum(n, self.time_mask_width))
+        count[:, tw_cols] = cap[:, None] + 1
+        tab = np.minimum((u * count).astype(np.int64), count - 1)               # c - W, w + W - 1, every fw and tw
+        # the offsets depend on the widths drawn above: f0 ~ U{0..D-fw}, t0 ~ U{0..n-tw}
+        count[:, fw_cols - 1] = D - tab[:, fw_cols] + 1
+        count[:, tw_cols - 1] = n[:, None] - tab[:, tw_cols] + 1
+        off_cols = np.concatenate([fw_cols, tw_cols]) - 1
+        tab[:, off_cols] = np.minimum((u[:, off_cols] * count[:, off_cols]).astype(np.int64), count[:, off_cols] - 1)
+        on = (n >= 2 * W + 2) & (W >= 2)
+        tab[:, 0] = np.where(on, tab[:, 0] + W, 0)
+        tab[:, 1] = np.where(on, tab[:, 1] - (W - 1), 0)
+        return torch.from_numpy(tab.astype(np.int32))
+
+    def __call__(self, feat, feat_len_host, seed, step, rank=0, feat_len_dev=None):
+        """feat [B, T, channels * feat_dim] on the GPU -> its augmented copy.  feat_len_host: the lengths as the collate
+        function returned them (host); feat_len_dev: the same lengths already on the device (int64) when the caller
+        has them, else they are uploaded here.  Nothing in here waits for the device."""
+        if feat.shape[-1] != self.channels * self.feat_dim:
+            raise ValueError('specaug: features are %d wide, policy was built for %d x %d' % (
+                feat.shape[-1], self.channels, self.feat_dim))
+        tab = self.sample(feat_len_host, seed, step, rank)
+        params = tab.pin_memory().to(feat.device, non_blocking=True)
+        if feat_len_dev is None:
+            feat_len_dev = torch.as_tensor(feat_len_host, dtype=torch.int64).reshape(-1).pin_memory().to(
+                feat.device, non_blocking=True)
+        with torch.no_grad():
+            return ops.spec_augment(feat, feat_len_dev, params, self.n_freq_mask, self.n_time_mask, self.mask_value,
+                                    channels=self.channels)
+
+    def create_msg(self):
+        return 'SpecAugment| time warp W = {} | {} freq. mask(s) <= {} of {} bins | {} time mask(s) <= min({}, {} * len) ' \
+               '| fill = {}'.format(self.time_warp, self.n_freq_mask, self.freq_mask_width, self.feat_dim,
+                                    self.n_time_mask, self.time_mask_width, self.time_mask_ratio, self.mask_value)
+
+
 def create_transform(audio_config, device='cuda'):
     ''' same contract as the reference (audio.py:115-133): pops feat_type / feat_dim / delta_order /
     delta_window_size / apply_cmvn, the rest are fbank kwargs; returns (Sequential, output dim) '''

@@ -740,6 +740,26 @@ int asrk_fbank_logmel_batch_f32(const void *wave, int sample_bytes, int64_t ld_w
                                 float *mel, int win, int shift, int log2n, float scale, float preemph, int remove_dc,
                                 float eps, void *stream);
 
+/* ---- SpecAugment on the padded feature batch (training input augmentation; the reference keeps the SpecAugment
+ * learning-rate schedules, src/optim.py:65-82, and augments nothing: the call sits between fetch_data and the model
+ * call of bin/train_asr.py:99-105) -----------------------------------------------------------------------------------
+ * x, y [B, T, ld] (x != y), ld >= C*D; column c*D + d = mel bin d of channel c (static / delta / delta-delta: the
+ * layout of Postprocess and asrk_delta_cmvn_batch_f32).  lens [B] int64 (device): n = valid frames of utterance b
+ * (clamped to 0..T).  params [B, P] int32 (device), P = 2 + 2*n_fmask + 2*n_tmask, row = c, w, f0_0, fw_0, ..,
+ * t0_0, tw_0, ..  (sampled on the host: src/audio.py SpecAugment.sample).
+ * Output frame t < n.  Time warp, active only when w != 0, 0 < c < n-1 and 0 < d = c+w < n-1 (else source = frame t):
+ *     t <= d: num = t*c, den = d;   t > d: num = c*(n-1-d) + (t-d)*(n-1-c), den = n-1-d   (64-bit integers)
+ *     i = num / den, r = num % den, j = min(i+1, n-1), a = (float)r / (float)den,
+ *     y[t] = (1-a)*x[i] + a*x[j], and y[t] = x[i] bit for bit when r == 0.
+ * The map is increasing, fixes frames 0 and n-1 and sends d to c; i and j are clamped to 0..n-1 whatever the row holds.
+ * Masks, after the warp, in output coordinates: mel bin d in any [f0_k, f0_k+fw_k) -> `fill` in every channel; frame t
+ * in any [t0_k, t0_k+tw_k) (t < n) -> `fill` in all C*D columns; zero or negative widths mask nothing.
+ * Frames t >= n are copied from x unchanged; columns >= C*D of y are not written.  One launch, no atomics.
+ * ASRK_ESHAPE: a negative size, ld < C*D, C*D > 16384, n_fmask / n_tmask outside 0..8, x == y, a NULL pointer with
+ * B*T > 0 (all checked before any device call); B*T == 0 returns 0 without a launch. */
+int asrk_spec_augment_f32(const float *x, float *y, int B, int T, int ld, int D, int C, const int64_t *lens,
+                          const int32_t *params, int n_fmask, int n_tmask, float fill, void *stream);
+
 /* ---- CTC loss (bin/train_asr.py:49,123-124 -> torch.nn.CTCLoss(blank=0)) ---------------
  * log_probs element (t,b,c) at lp[t*stride_t + b*stride_b + c]; targets [B,L] int64 (row stride
  * tgt_stride) zero-padded; input_lengths/target_lengths int64 [B].
