@@ -1,0 +1,51 @@
+"""The testing solver `main.py --test` runs: bin/test_asr.py's Solver, with pure-CTC beam search WITH RNN-LM
+fusion decoded in groups as well.
+
+bin/test_asr.py decodes `ASRK_DECODE_BATCH` (default 16) utterances per `forward_batch` call of either decoder,
+but sets the group to one for CTC + LM, from the time when that search went one launch + one LM step per frame
+and utterance.  `CTCBeamDecoder.forward_batch` now advances the group in lock-step (one launch of U workgroups +
+ONE LM step over all U x beam rows per frame: `search_device_batch`), so this solver hands it groups; everything
+else - greedy decoding, the joint CTC-attention search, CTC search without an LM, output files, the fan-out over
+ranks - is the parent class's.  `ASRK_DECODE_BATCH=1` still restores one utterance at a time.
+"""
+import os
+
+from . import test_asr
+from ..parallel import gather_in_order
+
+
+class Solver(test_asr.Solver):
+    ''' Solver for testing '''
+
+    def exec(self):
+        group = max(1, int(os.environ.get('ASRK_DECODE_BATCH', '16')))
+        if self.greedy or not self.ctc_only or not self.decoder.apply_lm or group == 1:
+            return super().exec()
+        dcfg = self.config['decode']
+        for s, ds in zip(['dev', 'test'], [self.dv_set, self.tt_set]):
+            # files and messages as in the parent's beam branch (bin/test_asr.py: exec)
+            self.cur_output_path = self.output_file.format(s, 'output')
+            self.cur_beam_path = self.output_file.format(
+                s, 'beam-{}-{}'.format(dcfg['beam_size'], dcfg.get('lm_weight', 0.0)))
+            if self.rank == 0:
+                with open(self.cur_output_path, 'w', encoding='UTF-8') as f:
+                    f.write('idx\thyp\ttruth\n')
+                with open(self.cur_beam_path, 'w') as f:
+                    f.write('idx\tbeam\thyp\ttruth\n')
+            self.verbose('Performing instance-wise CTC beam decoding on {} set, num of batch = {}.'.format(s, len(ds)))
+            mine, ids, n_utt = self._my_share(ds)
+            local, pending = [], []
+            for k, data in enumerate(mine):
+                self.progress('Decode - {}/{}'.format(ids[k] + 1, n_utt))
+                pending.append(data)
+                if len(pending) == group:
+                    local += test_asr.ctc_beam_decode_many(pending, self.decoder, self.device)
+                    pending = []
+            if pending:
+                local += test_asr.ctc_beam_decode_many(pending, self.decoder, self.device)
+            results = gather_in_order(local, n_utt, self.dist, self.rank, self.world)
+            if results is None:          # not rank 0: its rows have been handed over
+                continue
+            self.verbose('Results/Beams will be stored at {} / {}.'.format(self.cur_output_path, self.cur_beam_path))
+            self.write_hyp(results, self.cur_output_path, self.cur_beam_path)
+        self.verbose('All done !')

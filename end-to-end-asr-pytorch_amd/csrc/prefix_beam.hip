@@ -15,12 +15,14 @@
 #define PB_FOR(i, n) for (int i = (int)threadIdx.x; i < (n); i += (int)blockDim.x)
 #define PB_SYNC() __syncthreads()
 #define PB_TID0 (threadIdx.x == 0)
-// optional phase timeline (tools/ctc_beam_bench.py --timeline): thread 0 stamps the shader clock after every phase
+// optional phase timeline (tools/ctc_beam_bench.py --timeline): thread 0 stamps the shader clock after every phase; in a
+// multi-workgroup launch (PB_WG0 = 1, a template argument of the functions that stamp) only workgroup 0 does - the
+// one-workgroup kernel is compiled without the test
 __device__ unsigned long long *pb_dbg_ptr = nullptr;
 __device__ int pb_dbg_frame = 0;
 #define PB_STAMP(k)                                                                                     \
     do {                                                                                                \
-        if (pb_dbg_ptr && threadIdx.x == 0 && pb_dbg_frame < 64) pb_dbg_ptr[pb_dbg_frame * 16 + (k)] = wall_clock64(); \
+        if (pb_dbg_ptr && threadIdx.x == 0 && (!PB_WG0 || blockIdx.x == 0) && pb_dbg_frame < 64) pb_dbg_ptr[pb_dbg_frame * 16 + (k)] = wall_clock64(); \
     } while (0)
 __device__ __forceinline__ double pb_exp(double v) { return exp(v); }
 __device__ __forceinline__ double pb_log1p(double v) { return log1p(v); }
@@ -230,11 +232,12 @@ __device__ void pb_rank_row(const PBState &s, float *psc_l, int *pv_l, int row, 
     __syncthreads();
 }
 
-__global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PBLaunch p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char pb_lds[];
-    PBState s = p.s;
-    // ---- carve the per-frame scratch out of LDS
-    unsigned char *q = pb_lds;
+// the per-frame scratch of one workgroup, carved out of its dynamic LDS (lds_bytes below)
+struct PBRankLds {
+    float *psc;                  // [8 waves][C] stage-1 survivors of pb_rank_row
+    int *pv;
+};
+__device__ __forceinline__ PBRankLds pb_carve_lds(PBState &s, unsigned char *q) {
     auto take = [&](size_t bytes) { unsigned char *r = q; q += (bytes + 15) & ~(size_t)15; return r; };
     s.e_pb = (double *)take(PB_MAX_ENTRIES * 8); s.e_pnb = (double *)take(PB_MAX_ENTRIES * 8);
     s.e_sc = (double *)take(PB_MAX_ENTRIES * 8); s.e_dig = (unsigned long long *)take(PB_MAX_ENTRIES * 8);
@@ -253,46 +256,116 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PBLaunch p) {
     s.scal = (int *)take(16);
     s.w_key = (double *)take((size_t)(PB_THREADS / 64) * PB_MAX_BEAM * 8);
     s.w_pos = (int *)take((size_t)(PB_THREADS / 64) * PB_MAX_BEAM * 4);
-    float *psc_l = (float *)take((size_t)(PB_THREADS / 64) * s.C * 4);
-    int *pv_l = (int *)take((size_t)(PB_THREADS / 64) * s.C * 4);
+    PBRankLds rk;
+    rk.psc = (float *)take((size_t)(PB_THREADS / 64) * s.C * 4);
+    rk.pv = (int *)take((size_t)(PB_THREADS / 64) * s.C * 4);
     s.bnd = take(PB_MAX_ENTRIES);
     s.t_dif = (signed char *)take(PB_PAIRS); s.t_pre = take(PB_PAIRS);
+    return rk;
+}
 
-    int cur = p.cur;
-    if (p.init) {
-        // B = [CTCHypothesis()]: empty sequence, Pr- = 0, Pr+ = LOG_ZERO, updated_lm = True when an LM is fused
-        if (threadIdx.x == 0) {
-            const PBBeam &b = s.beam[cur];
-            b.len[0] = 0; b.slen[0] = 0; b.pb[0] = 0.0; b.pnb[0] = PB_LOG_ZERO; b.upd[0] = 1;
-            b.lcp[0] = 0; b.dif[0] = 0; b.pre[0] = 1; b.tail[0] = 0ull;
-            s.nb[cur] = 1;
-        }
+// B = [CTCHypothesis()]: empty sequence, Pr- = 0, Pr+ = LOG_ZERO, updated_lm = True when an LM is fused
+__device__ __forceinline__ void pb_init_beam(const PBState &s, int cur) {
+    if (threadIdx.x == 0) {
+        const PBBeam &b = s.beam[cur];
+        b.len[0] = 0; b.slen[0] = 0; b.pb[0] = 0.0; b.pnb[0] = PB_LOG_ZERO; b.upd[0] = 1;
+        b.lcp[0] = 0; b.dif[0] = 0; b.pre[0] = 1; b.tail[0] = 0ull;
+        s.nb[cur] = 1;
+    }
+    __syncthreads();
+}
+
+// one frame x [V] of the search: candidate ranking (per row with an LM, once - row 0 - without), then pb_frame
+template <int PB_WG0>
+__device__ __forceinline__ void pb_rank_and_frame(const PBState &s, PBRankLds rk, int cur, const float *x,
+                                                  const float *lm, float lw, const unsigned char *allowed,
+                                                  int last_frame, int lm_follows) {
+    const int nb = s.nb[cur];
+    PB_STAMP(0);
+    const int rows = lm ? nb : 1;
+    if (rows > 1 && s.V <= 64 * PB_RW) {                  // several rows (LM fusion): one wave per row, 8 at a time
+        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        for (int i = wave; i < rows; i += PB_THREADS / 64)
+            pb_rank_wave(s, i, x, lm + (size_t)i * s.V, lw, allowed, lane);
+        __syncthreads();
+    } else {
+        for (int i = 0; i < rows; ++i)
+            pb_rank_row(s, rk.psc, rk.pv, i, x, lm ? lm + (size_t)i * s.V : nullptr, lw, allowed);
+    }
+    if (!lm) {
+        PB_FOR(z, (nb - 1) * s.C) s.cand[s.C + z] = s.cand[z % s.C];
         __syncthreads();
     }
+    PB_STAMP(15);
+    pb_frame<PB_WG0>(s, cur, x, lm, lw, last_frame, lm_follows);
+}
+
+__global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PBLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pb_lds[];
+    PBState s = p.s;
+    const PBRankLds rk = pb_carve_lds(s, pb_lds);
+    int cur = p.cur;
+    if (p.init) pb_init_beam(s, cur);
     for (int t = p.t0; t < p.t1; ++t) {
-        const float *x = p.ctc + (size_t)t * s.V;
-        const int nb = s.nb[cur];
-        PB_STAMP(0);
-        // candidate ranking: per row with an LM, once (row 0) without
-        const int rows = p.lm ? nb : 1;
-        if (rows > 1 && s.V <= 64 * PB_RW) {                  // several rows (LM fusion): one wave per row, 8 at a time
-            const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-            for (int i = wave; i < rows; i += PB_THREADS / 64)
-                pb_rank_wave(s, i, x, p.lm + (size_t)i * s.V, p.lw, p.allowed, lane);
-            __syncthreads();
-        } else {
-            for (int i = 0; i < rows; ++i)
-                pb_rank_row(s, psc_l, pv_l, i, x, p.lm ? p.lm + (size_t)i * s.V : nullptr, p.lw, p.allowed);
-        }
-        if (!p.lm) {
-            PB_FOR(z, (nb - 1) * s.C) s.cand[s.C + z] = s.cand[z % s.C];
-            __syncthreads();
-        }
-        PB_STAMP(15);
-        pb_frame(s, cur, x, p.lm, p.lw, t == p.T - 1, p.lm_follows);
+        pb_rank_and_frame<0>(s, rk, cur, p.ctc + (size_t)t * s.V, p.lm, p.lw, p.allowed, t == p.T - 1, p.lm_follows);
         if (pb_dbg_ptr && threadIdx.x == 0) pb_dbg_frame += 1;
         cur ^= 1;
     }
+}
+
+// U utterances in lock-step, ONE frame per launch (LM fusion: the caller steps the RNN-LM for all U x W rows between
+// launches).  Workgroup u searches frame t_start[u] + j of utterance u in its own workspace slab - the same phases,
+// scratch and arithmetic as prefix_beam_kernel - and exports the LM bookkeeping of its W rows as GLOBAL row indices
+// of the caller's [U * W] LM batch.  An utterance that is all blank (t_start < 0) or has no frame left leaves before
+// the first barrier without touching its slab: its rows keep their LM state (identity indices).
+struct PBMultiLaunch {
+    PBState s;                   // table pointers of slab 0
+    size_t slab_stride;          // bytes between the slabs of two utterances
+    const float *ctc;            // [U][Tmax] rows of V log-probs, row_stride floats apart
+    long long row_stride;
+    const float *lm;             // [U * W][V]
+    const unsigned char *allowed;
+    const int *frames, *t_start; // [U]
+    int *parent, *last, *gidx;   // [U * W]
+    float lw;
+    int U, Tmax, j;
+};
+
+template <typename T>
+__device__ __forceinline__ void pb_shift(T *&ptr, size_t bytes) {
+    ptr = reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(ptr) + bytes);
+}
+
+__global__ __launch_bounds__(PB_THREADS) void prefix_beam_multi_kernel(PBMultiLaunch p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pb_lds[];
+    const int u = blockIdx.x, W = p.s.W, base = u * W;
+    const int ts = p.t_start[u], Tu = min(p.frames[u], p.Tmax);
+    if (ts < 0 || p.j >= Tu - ts) {                           // uniform over the workgroup
+        PB_FOR(r, W) {
+            p.parent[base + r] = base + r; p.gidx[base + r] = base + r;
+            if (p.j == 0) p.last[base + r] = 0;               // later: the token already there
+        }
+        return;
+    }
+    const int t = ts + p.j;
+    PBState s = p.s;
+    {
+        const size_t off = (size_t)u * p.slab_stride;
+        auto shift = [&](auto *&ptr) { pb_shift(ptr, off); };
+        for (int k = 0; k < 2; ++k) {
+            PBBeam &b = s.beam[k];
+            shift(b.len); shift(b.slen); shift(b.tok); shift(b.str); shift(b.pb); shift(b.pnb); shift(b.upd);
+            shift(b.lcp); shift(b.dif); shift(b.pre); shift(b.tail);
+        }
+        shift(s.nb); shift(s.out_parent); shift(s.out_last); shift(s.out_gidx);
+    }
+    const PBRankLds rk = pb_carve_lds(s, pb_lds);
+    const int cur = p.j & 1;
+    if (p.j == 0) pb_init_beam(s, cur);
+    pb_rank_and_frame<1>(s, rk, cur, p.ctc + ((size_t)u * p.Tmax + t) * (size_t)p.row_stride, p.lm + (size_t)base * s.V,
+                      p.lw, p.allowed, t == Tu - 1, t < Tu - 1);
+    pb_export_rows(s, 1 - cur, u, p.U, p.parent, p.last, p.gidx);
+    if (pb_dbg_ptr && threadIdx.x == 0 && blockIdx.x == 0) pb_dbg_frame += 1;
 }
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -401,6 +474,59 @@ extern "C" int asrk_ctc_prefix_beam_f32(const float *ctc, int T, int V, const un
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     if (lds > 150 * 1024) return ASRK_ESHAPE;
     hipLaunchKernelGGL(prefix_beam_kernel, dim3(1), dim3(PB_THREADS), lds, (hipStream_t)stream, p);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+// ---- U utterances in lock-step (LM fusion): one slab of the single-utterance layout for (beam, Tmax) per utterance
+extern "C" size_t asrk_ctc_prefix_beam_multi_ws_bytes(int U, int beam, int Tmax, size_t *slab_stride) {
+    const size_t slab = align16(asrk_ctc_prefix_beam_ws_bytes(beam, Tmax));
+    if (slab_stride) *slab_stride = slab;
+    if (U <= 0 || slab == 0) return 0;
+    return (size_t)U * slab;
+}
+
+extern "C" int asrk_ctc_prefix_beam_multi_f32(const float *ctc, int64_t ctc_row_stride, int U, int Tmax, int V,
+                                              const unsigned char *allowed, int beam, int cand, const float *lm,
+                                              float lm_weight, const int *frames, const int *t_start, int j,
+                                              int *out_parent, int *out_last, int *out_gidx, void *ws,
+                                              size_t ws_bytes, void *stream) {
+    if (U <= 0 || U > (1 << 20) || Tmax <= 0 || V <= 0 || V > 99999 || beam <= 0 || beam > PB_MAX_BEAM || cand <= 0 ||
+        cand > V)
+        return ASRK_EINVAL;
+    if ((size_t)beam * (cand + 1) > PB_MAX_ENTRIES || V > PB_MAX_V) return ASRK_ESHAPE;
+    if (j < 0 || j >= Tmax || ctc_row_stride < V) return ASRK_EINVAL;
+    if (!ctc || !allowed || !lm || !frames || !t_start || !out_parent || !out_last || !out_gidx || !ws) return ASRK_EINVAL;
+    const int Lcap = Tmax + 1, Scap = 5 * Lcap;
+    const WsLayout l = ws_layout(beam, Lcap, Scap);
+    const size_t slab = align16(l.total);
+    if (ws_bytes < (size_t)U * slab) return ASRK_EWORKSPACE;
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return ASRK_EINVAL;
+    const size_t lds = lds_bytes(beam, cand, V);
+    if (lds > 150 * 1024) return ASRK_ESHAPE;
+    unsigned char *w = reinterpret_cast<unsigned char *>(ws);
+    PBMultiLaunch p{};
+    PBState &s = p.s;
+    s.W = beam; s.C = cand; s.V = V; s.Lcap = Lcap; s.Scap = Scap;
+    for (int k = 0; k < 2; ++k) {
+        s.beam[k].pb = (double *)(w + l.pb[k]); s.beam[k].pnb = (double *)(w + l.pnb[k]);
+        s.beam[k].tok = (int *)(w + l.tok[k]); s.beam[k].str = w + l.str[k];
+        s.beam[k].len = (int *)(w + l.len[k]); s.beam[k].slen = (int *)(w + l.slen[k]);
+        s.beam[k].upd = (int *)(w + l.upd[k]);
+        s.beam[k].lcp = (int *)(w + l.lcp[k]); s.beam[k].dif = (signed char *)(w + l.dif[k]);
+        s.beam[k].pre = w + l.pre[k]; s.beam[k].tail = (unsigned long long *)(w + l.tail[k]);
+    }
+    s.nb = (int *)(w + l.nb);
+    s.out_parent = (int *)(w + l.outp); s.out_last = (int *)(w + l.outl); s.out_gidx = (int *)(w + l.outg);
+    p.slab_stride = slab;
+    p.ctc = ctc; p.row_stride = ctc_row_stride; p.lm = lm; p.allowed = allowed; p.lw = lm_weight;
+    p.frames = frames; p.t_start = t_start; p.parent = out_parent; p.last = out_last; p.gidx = out_gidx;
+    p.U = U; p.Tmax = Tmax; p.j = j;
+    // per call, as in asrk_ctc_prefix_beam_f32: the attribute belongs to the current device's copy of the kernel, so a
+    // latched flag would be wrong on a second GPU or thread (a host-side call next to a ~1 ms lock-step frame)
+    ASRK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(prefix_beam_multi_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    hipLaunchKernelGGL(prefix_beam_multi_kernel, dim3(U), dim3(PB_THREADS), lds, (hipStream_t)stream, p);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
 }

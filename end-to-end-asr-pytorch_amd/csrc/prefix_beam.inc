@@ -24,7 +24,8 @@
 // the host build).
 //
 // Required before inclusion: PB_HD (function qualifier), PB_FOR(i, n) { ... }, PB_SYNC(), PB_TID0 (true for the
-// one thread that publishes scalars), pb_exp(double), pb_log1p(double), PB_STAMP(k) (phase time stamp; may be empty).
+// one thread that publishes scalars), pb_exp(double), pb_log1p(double), PB_STAMP(k) (phase time stamp; may be empty;
+// it may refer to pb_frame's template argument PB_WG0: 1 = the launch has several workgroups, stamp from the first).
 #pragma once
 #include <stdint.h>
 
@@ -165,6 +166,7 @@ PB_HD inline bool pb_same_seq(const PBState &s, const PBBeam &b, int e1, int e2)
 // (lw = float32(lm_weight)); s.cand [nb][C] = this frame's candidate symbols per row (filled by the caller's
 // ranking phase); last_frame selects the length-normalised final score; lm_step_follows = an LM update will be
 // run after this frame (t < T - 1) so out_gidx / upd are set accordingly.
+template <int PB_WG0 = 0>
 PB_HD inline void pb_frame(const PBState &s, int cur, const float *x, const float *lm, float lw, int last_frame,
                            int lm_step_follows) {
     const PBBeam &b = s.beam[cur];
@@ -410,4 +412,23 @@ PB_HD inline void pb_frame(const PBState &s, int cur, const float *x, const floa
     if (PB_TID0) { s.nb[1 - cur] = nbn; s.scal[2] = nbn; }
     PB_SYNC();
     PB_STAMP(10);
+}
+
+// Lock-step search of U utterances (one LM batch of U * W rows, rows u*W .. u*W+W-1 = utterance u): the LM
+// bookkeeping pb_frame left for the rows of beam buffer `buf` of utterance u, as GLOBAL row indices.  parent /
+// gidx index cat([old rows, stepped rows]) of the U * W row batch: a row that inherits its state names its parent's
+// old row, a row whose LM is stepped names its own row in the stepped half.  Dead rows keep their own state
+// (identity) and feed token 0, so the batched LM step sees valid indices in every row.
+PB_HD inline void pb_export_rows(const PBState &s, int buf, int u, int U, int *parent, int *last, int *gidx) {
+    const int W = s.W, base = u * W, nbn = s.nb[buf];
+    PB_FOR(r, W) {
+        if (r < nbn) {
+            const int g = s.out_gidx[r];
+            parent[base + r] = base + s.out_parent[r];
+            last[base + r] = s.out_last[r];
+            gidx[base + r] = g >= W ? U * W + base + (g - W) : base + g;
+        } else {
+            parent[base + r] = base + r; last[base + r] = 0; gidx[base + r] = base + r;
+        }
+    }
 }

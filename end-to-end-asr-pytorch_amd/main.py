@@ -52,7 +52,7 @@ def main(argv=None):
         mode = 'train'
     elif paras.test:
         assert paras.load is None, 'Load option is mutually exclusive to --test'
-        from .bin.test_asr import Solver
+        from .bin.decode_asr import Solver     # bin/test_asr.py's solver + grouped CTC search with LM fusion
         mode = 'test'
     else:
         from .bin.train_asr import Solver

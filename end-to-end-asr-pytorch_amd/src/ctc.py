@@ -286,19 +286,107 @@ class CTCBeamDecoder(nn.Module):
         return read_back(cur)
 
     @torch.no_grad()
+    def search_device_batch(self, ctc_dev, lens, return_ws=False):
+        """search_device with LM fusion for U utterances in lock-step: ctc_dev [U, Tmax, V] log-probs (rows of a
+        packed encoder pass; frames >= lens[u] are never read), lens [U] frame counts -> U hypothesis lists, each
+        what search_device returns for ctc_dev[u, :lens[u]] alone.  Step j searches frame t_start_u + j of every
+        utterance that still has one in ONE launch of U workgroups (asrk_ctc_prefix_beam_multi_f32), then ONE
+        self.lm call steps all U * beam rows and one index_select per LM tensor applies the kernel's gather
+        indices; utterances that are finished (or all blank) keep their rows.  Read back: the batch's arg-max
+        before the loop, all hypotheses in one copy after it.
+        return_ws=True: also the workspace as an int32 tensor [U, slab // 4] (one slab per utterance, laid out as
+        asrk_ctc_prefix_beam_ws_offsets(beam, Tmax, ...) says; for tests)."""
+        import ctypes
+        from .. import _lib
+        assert self.apply_lm, "the lock-step search exists for LM fusion (without an LM: forward_batch's streams)"
+        L = _lib.load()
+        dev = ctc_dev.device
+        U, Tmax, V = ctc_dev.shape
+        W, C = self.beam_size, self.vocab_cand
+        if ctc_dev.dtype != torch.float32 or ctc_dev.stride(2) != 1 or ctc_dev.stride(1) < V or \
+                ctc_dev.stride(0) != Tmax * ctc_dev.stride(1):
+            ctc_dev = ctc_dev.float().contiguous()
+        T_h = [int(v) for v in torch.as_tensor(lens).cpu().tolist()]
+        assert len(T_h) == U and all(0 < t <= Tmax for t in T_h)
+        amax = ops.argmax(ctc_dev).cpu().numpy()                               # [U, Tmax]: the one read-back before the loop
+        ts_h = []
+        for u in range(U):
+            nz = np.nonzero(amax[u, :T_h[u]] != 0)[0]
+            ts_h.append(int(nz[0]) if len(nz) else -1)
+        steps = [T_h[u] - ts_h[u] if ts_h[u] >= 0 else 0 for u in range(U)]
+        if max(steps) == 0:
+            hyps = [[[]] for _ in range(U)]                                    # search_device's answer for each of them
+            return (hyps, None) if return_ws else hyps
+        allowed = torch.zeros((V,), dtype=torch.uint8)
+        allowed[torch.as_tensor(self.vocab_range)] = 1
+        allowed = allowed.to(dev)
+        meta = torch.tensor([T_h, ts_h, [s & 1 for s in steps]], dtype=torch.int32).to(dev)   # frames, t_start, final buffer
+        slab = ctypes.c_size_t(0)
+        nws = int(L.asrk_ctc_prefix_beam_multi_ws_bytes(U, W, Tmax, ctypes.byref(slab)))
+        slab = int(slab.value)
+        ws = torch.zeros((nws,), dtype=torch.uint8, device=dev)
+        book = torch.zeros((3, U * W), dtype=torch.int32, device=dev)          # parent, last token, gather index
+        stream = ops._stream
+
+        out, hid = self.lm(torch.zeros((1, 1), dtype=torch.long, device=dev), torch.ones(1, dtype=torch.long), None)
+        lstm = isinstance(hid, tuple)
+        lm_rows = torch.zeros((U * W, V), dtype=torch.float32, device=dev)     # <sos> step -> row 0 of every utterance
+        lm_rows[0::W] = ops.log_softmax(out).reshape(1, V)
+        states = []
+        for x in (list(hid) if lstm else [hid]):                               # each [n_layers, rows, dim]
+            st = x.new_zeros(x.shape[0], U * W, x.shape[2])
+            st[:, 0::W] = x
+            states.append(st)
+        ones = torch.ones(U * W, dtype=torch.long)
+        for j in range(max(steps)):
+            _lib.check(L.asrk_ctc_prefix_beam_multi_f32(
+                ops._p(ctc_dev), ctc_dev.stride(1), U, Tmax, V, ops._p(allowed), W, C, ops._p(lm_rows),
+                float(self.lm_w), ops._p(meta[0]), ops._p(meta[1]), j, ops._p(book[0]), ops._p(book[1]),
+                ops._p(book[2]), ops._p(ws), nws, stream()), "ctc_prefix_beam_multi")
+            if any(j < s_ - 1 for s_ in steps):                                # some utterance has a following frame
+                parent, last, gidx = book.long().unbind(0)
+                h_in = [x.index_select(1, parent) for x in states]
+                out, hid = self.lm(last.view(U * W, 1), ones, (h_in[0], h_in[1]) if lstm else h_in[0])
+                stepped = list(hid) if lstm else [hid]
+                lm_rows = torch.cat([lm_rows, ops.log_softmax(out).reshape(U * W, V)], 0).index_select(0, gidx)
+                states = [torch.cat([o_, n_], 1).index_select(1, gidx) for o_, n_ in zip(states, stepped)]
+
+        # all hypotheses in one copy: per utterance the live-row count, lengths and tokens of ITS final buffer
+        wsi = ws.view(torch.int32).view(U, slab // 4)
+        o = [[ctypes.c_int64(0) for _ in range(6)] for _ in range(2)]
+        for buf in (0, 1):
+            _lib.check(L.asrk_ctc_prefix_beam_ws_offsets(W, Tmax, buf, *[ctypes.byref(v) for v in o[buf]]),
+                       "beam offsets")
+        (nb0, len0, tok0), (nb1, len1, tok1) = ([int(v.value) // 4 for v in o[buf][:3]] for buf in (0, 1))
+        n_tok = W * (Tmax + 1)
+        pick = meta[2].bool().unsqueeze(1)
+        res = torch.cat([torch.where(pick, wsi[:, a1:a1 + n], wsi[:, a0:a0 + n])
+                         for a0, a1, n in ((nb0, nb1, 1), (len0, len1, W), (tok0, tok1, n_tok))], 1).cpu()
+        hyps = []
+        for u in range(U):
+            if steps[u] == 0:
+                hyps.append([[]])
+                continue
+            nb, ln = int(res[u, 0]), res[u, 1:1 + W].tolist()
+            toks = res[u, 1 + W:].view(W, Tmax + 1)
+            hyps.append([toks[r, :ln[r]].tolist() for r in range(nb)])
+        return (hyps, wsi) if return_ws else hyps
+
+    @torch.no_grad()
     def forward_batch(self, feat, feat_len, n_streams=16):
         ''' CTC prefix beam search over U utterances at once: feat [U,Tmax,D] zero-padded, feat_len [U] -> U result
             lists, each what forward() returns for that utterance alone.  One packed encoder pass (every utterance
             encoded as if alone, Encoder.forward(packed=True)), then every utterance's search - ONE launch of the
             one-workgroup prefix-beam kernel (csrc/prefix_beam.hip) - goes to its own stream: the searches run side
             by side on different CUs (the reference's parallel axis, bin/test_asr.py:163-167, on one GPU).  With LM
-            fusion (one launch + one LM step per frame) or outside the kernel's limits: one forward() each. '''
+            fusion the utterances advance in lock-step instead (search_device_batch: one launch of U workgroups +
+            one LM step over all U * beam rows per frame).  Outside the kernel's limits: one forward() each. '''
         U = feat.shape[0]
         lens_h = [int(v) for v in torch.as_tensor(feat_len).cpu().tolist()]
         asr = self.asr
         one_by_one = lambda: [self.forward(feat[u:u + 1, :lens_h[u]].contiguous(),
                                            torch.as_tensor(feat_len)[u:u + 1]) for u in range(U)]
-        if U == 1 or self.apply_lm or not hasattr(asr, 'encoder') or not asr.encoder.supports_packed() \
+        if U == 1 or not hasattr(asr, 'encoder') or not asr.encoder.supports_packed() \
                 or not self._device_search_ok(asr.vocab_size):
             return one_by_one()
         dev = feat.device
@@ -306,6 +394,8 @@ class CTCBeamDecoder(nn.Module):
         ctc = ops.log_softmax(ops.linear(enc, asr.ctc_layer.weight, asr.ctc_layer.bias))
         ctc = ops.log_softmax(ctc)               # the reference re-applies log_softmax (forward() below)
         enc_len_h = [int(v) for v in asr.encoder.packed_frames.cpu().tolist()]   # forward() searches the whole tensor
+        if self.apply_lm:
+            return self.search_device_batch(ctc, enc_len_h)
         amax = ops.argmax(ctc).cpu().numpy()                                     # [U, T']
         main = torch.cuda.current_stream(dev)
         streams = [torch.cuda.Stream(device=dev) for _ in range(min(U, n_streams))]

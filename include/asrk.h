@@ -321,6 +321,31 @@ int asrk_ctc_prefix_beam_ws_offsets(int beam, int T, int buf, int64_t *nb_off, i
 int asrk_ctc_prefix_beam_f32(const float *ctc, int T, int V, const unsigned char *allowed, int beam, int cand,
                              const float *lm, float lm_weight, int t0, int t1, int cur_buf, int init,
                              int lm_step_follows, void *ws, size_t ws_bytes, void *stream);
+/* The same search for U utterances in LOCK-STEP with RNN-LM fusion: one launch of U workgroups per step j, then the
+ * caller steps the LM ONCE for all U * beam rows.  Workgroup u searches frame t_start[u] + j of utterance u with the
+ * phases, scratch and arithmetic of the single-utterance kernel, so its hypotheses do not depend on the batch.
+ *   ctc [U, Tmax, V]: frame t of utterance u at ctc + (u * Tmax + t) * ctc_row_stride floats (ctc_row_stride >= V);
+ *   allowed [V]: as above, shared by all utterances;
+ *   lm [U * beam, V] (required): rows u*beam .. u*beam + beam - 1 are the current beam rows of utterance u;
+ *   frames [U], t_start [U] (int32, device): frame count T_u (clamped to Tmax) and the first frame whose arg-max
+ *       is not blank; t_start[u] < 0 = all blank, the utterance never runs;
+ *   j >= 0: the lock-step index.  Utterance u runs frame t = t_start[u] + j while t < T_u: init = (j == 0), the
+ *       current beam buffer is j & 1, lm_step_follows = (t < T_u - 1), last frame = (t == T_u - 1) - its final
+ *       beam is in buffer (T_u - t_start[u]) & 1.  A workgroup with nothing to do leaves its slab untouched;
+ *   out_parent / out_last / out_gidx [U * beam] (int32, device): per LM row, as GLOBAL row indices - the row
+ *       whose LM state it continues (u*beam + i), the token to feed, and the index into cat([old rows, stepped
+ *       rows]) of its next state: u*beam + i = inherit old row, U*beam + u*beam + r = stepped row r.  Dead rows
+ *       and utterances that did not run export their own row (identity) and token 0 / the token already there:
+ *       one index_select per LM tensor, valid indices in every row.
+ *   ws: asrk_ctc_prefix_beam_multi_ws_bytes(U, beam, Tmax, &slab) bytes, 16-byte aligned, kept between the calls
+ *       of one batch: U slabs of `slab` bytes, each laid out as asrk_ctc_prefix_beam_ws_offsets(beam, Tmax, ...)
+ *       describes.  Limits as above (beam <= 32, beam * (cand + 1) <= 1024, V <= 16384), 1 <= U <= 2^20 (the
+ *       global row indices are int32). */
+size_t asrk_ctc_prefix_beam_multi_ws_bytes(int U, int beam, int Tmax, size_t *slab_stride);
+int asrk_ctc_prefix_beam_multi_f32(const float *ctc, int64_t ctc_row_stride, int U, int Tmax, int V,
+                                   const unsigned char *allowed, int beam, int cand, const float *lm, float lm_weight,
+                                   const int *frames, const int *t_start, int j, int *out_parent, int *out_last,
+                                   int *out_gidx, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- attention decoder step (src/module.py:179-258, src/asr.py:277-313) -------------------
  * BN = B*num_head rows ordered (b, head).  All tensors contiguous f32; lens int64 [B].

@@ -4,6 +4,7 @@ at the reference's decode configuration (config/libri/ctc_decode_example.yaml: b
 V = 5000 symbols and T' = 200 encoder frames (a 16-s utterance at 8x time reduction).
 
     python tools/ctc_beam_bench.py [--out gpurun_out/ctc_beam.json]
+    python tools/ctc_beam_bench.py --lm-batch 1,4,16,32 [--V 16000]     # LM fusion: U utterances in lock-step
 """
 import argparse
 import importlib
@@ -35,17 +36,23 @@ def main():
     ap.add_argument("--beam", type=int, default=20)
     ap.add_argument("--cand", type=int, default=30)
     ap.add_argument("--timeline", action="store_true")
+    ap.add_argument("--lm-batch", default="", metavar="U[,U...]",
+                    help="only LM fusion: U utterances in lock-step (search_device_batch) against one at a time")
+    ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
     ctc = importlib.import_module(PKG + ".src.ctc")
-    g = torch.Generator().manual_seed(0)
-    logits = torch.randn(args.T, args.V, generator=g) * 1.5
-    logits[:, 0] += 9.0                                         # blank dominates most frames, as in a trained model
-    spikes = torch.randperm(args.T, generator=g)[:args.T // 4]  # ~50 emitting frames
-    logits[spikes, 0] -= 9.0
-    x = torch.log_softmax(logits, -1)
+
+    def posteriors(seed):
+        g = torch.Generator().manual_seed(seed)
+        logits = torch.randn(args.T, args.V, generator=g) * 1.5
+        logits[:, 0] += 9.0                                         # blank dominates most frames, as in a trained model
+        spikes = torch.randperm(args.T, generator=g)[:args.T // 4]  # ~50 emitting frames
+        logits[spikes, 0] -= 9.0
+        return torch.log_softmax(logits, -1)
+
+    x = posteriors(0)
     xd = x.cuda().contiguous()
     vr = [1] + list(range(3, args.V))
-    dec = ctc.CTCBeamDecoder(Stub(args.V), vr, args.beam, args.cand)
 
     def timed(fn, reps):
         fn()
@@ -56,6 +63,50 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / reps, out
 
+    def lm_decoder():
+        """the reference's default fusion (ctc_decode_example.yaml: lm_weight 0.5, lm_example.yaml: 2 x LSTM-1024 over
+        the same vocabulary), seeded random weights"""
+        import tempfile
+        import yaml
+        lm_mod = importlib.import_module(PKG + ".src.lm")
+        lm_cfg = dict(emb_tying=False, emb_dim=1024, module="LSTM", dim=1024, n_layers=2, dropout=0.0)
+        tmp = tempfile.mkdtemp()
+        torch.manual_seed(3)
+        lm = lm_mod.RNNLM(args.V, **lm_cfg)
+        yaml.safe_dump({"model": lm_cfg}, open(os.path.join(tmp, "lm.yaml"), "w"))
+        torch.save({"model": lm.state_dict()}, os.path.join(tmp, "lm.pth"))
+        return ctc.CTCBeamDecoder(Stub(args.V), vr, args.beam, args.cand, lm_path=os.path.join(tmp, "lm.pth"),
+                                  lm_config=os.path.join(tmp, "lm.yaml"), lm_weight=0.5, device="cuda")
+
+    if args.lm_batch:
+        # U different utterances of T frames in lock-step: one launch of U workgroups + ONE LM step over U x beam rows
+        # per frame, against the same utterances one at a time (one launch + one LM step of beam rows per frame each)
+        Us = [int(v) for v in args.lm_batch.split(",")]
+        dec_lm = lm_decoder()
+        xs = torch.stack([posteriors(u) for u in range(max(Us))]).cuda()
+        audio_s = args.T * 8 * 0.01
+        n_one = min(4, max(Us))
+        one = lambda: [dec_lm.search_device(xs[u]) for u in range(n_one)]
+        with torch.no_grad():
+            t_a, h_one = timed(one, args.reps)                    # one at a time before and after the lock-step runs
+            lock = {U: timed(lambda: dec_lm.search_device_batch(xs[:U], [args.T] * U), args.reps) for U in Us}
+            t_b, _ = timed(one, args.reps)
+        t_one = 0.5 * (t_a + t_b) / n_one
+        res = {"config": vars(args), "audio_seconds": audio_s,
+               "one_at_a_time": {"s_per_utt": t_one, "s_per_utt_before_after": [t_a / n_one, t_b / n_one],
+                                 "utt_per_s": 1.0 / t_one, "ms_per_frame": t_one / args.T * 1e3},
+               "lock_step": {}}
+        for U, (t, h) in lock.items():
+            res["lock_step"][str(U)] = {
+                "s_per_batch": t, "utt_per_s": U / t, "ms_per_frame": t / args.T * 1e3, "rtf": t / (U * audio_s),
+                "speedup_vs_one_at_a_time": (U / t) * t_one, "lm_rows": U * args.beam,
+                "hypotheses_equal_one_at_a_time": [h[u] == h_one[u] for u in range(min(U, n_one))]}
+        print(json.dumps(res, indent=1))
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+
+    dec = ctc.CTCBeamDecoder(Stub(args.V), vr, args.beam, args.cand)
     t_dev, h_dev = timed(lambda: dec.search_device(xd), 10)
     if args.timeline:
         import ctypes
@@ -100,17 +151,7 @@ def main():
     t_host, h_host = timed(lambda: dec._search_host(xd), 1)
     # with RNN-LM shallow fusion (the reference's default ctc_decode_example.yaml: lm_weight 0.5, lm_example.yaml:
     # 2 x LSTM-1024 over the same vocabulary): one launch per frame + a batched LM step, nothing read back
-    import tempfile
-    import yaml
-    lm_mod = importlib.import_module(PKG + ".src.lm")
-    lm_cfg = dict(emb_tying=False, emb_dim=1024, module="LSTM", dim=1024, n_layers=2, dropout=0.0)
-    tmp = tempfile.mkdtemp()
-    torch.manual_seed(3)
-    lm = lm_mod.RNNLM(args.V, **lm_cfg)
-    yaml.safe_dump({"model": lm_cfg}, open(os.path.join(tmp, "lm.yaml"), "w"))
-    torch.save({"model": lm.state_dict()}, os.path.join(tmp, "lm.pth"))
-    dec_lm = ctc.CTCBeamDecoder(Stub(args.V), vr, args.beam, args.cand, lm_path=os.path.join(tmp, "lm.pth"),
-                                lm_config=os.path.join(tmp, "lm.yaml"), lm_weight=0.5, device="cuda")
+    dec_lm = lm_decoder()
     with torch.no_grad():
         t_dev_lm, h_dev_lm = timed(lambda: dec_lm.search_device(xd), 3)
         t_host_lm, h_host_lm = timed(lambda: dec_lm._search_host(xd), 1)
