@@ -7,17 +7,43 @@ and utterance.  `CTCBeamDecoder.forward_batch` now advances the group in lock-st
 ONE LM step over all U x beam rows per frame: `search_device_batch`), so this solver hands it groups; everything
 else - greedy decoding, the joint CTC-attention search, CTC search without an LM, output files, the fan-out over
 ranks - is the parent class's.  `ASRK_DECODE_BATCH=1` still restores one utterance at a time.
+
+The optional key `decode: {align: true}` turns the run into CTC forced alignment of both sets to their reference
+transcripts instead of decoding (bin/align_asr.py); without the key nothing here changes.
 """
 import os
 
-from . import test_asr
+from . import align_asr, test_asr
 from ..parallel import gather_in_order
 
 
 class Solver(test_asr.Solver):
     ''' Solver for testing '''
 
+    def __init__(self, config, paras, mode):
+        self.align = bool(config['decode'].get('align', False))
+        if self.align:
+            # the search settings are not used, but the parent reads beam_size: 1 makes it take its greedy set-up
+            # (batch size of the training config) ...
+            config['decode'].setdefault('beam_size', 1)
+        super().__init__(config, paras, mode)
+        if self.align:
+            # ... which is replaced here by instance-wise loaders, like beam decoding.  This relies on the order
+            # main.py keeps: load_data() builds the loaders from self.config AFTER __init__ has returned
+            self.config['data']['corpus']['batch_size'] = 1
+
+    def set_model(self):
+        if not getattr(self, 'align', False):
+            return super().set_model()
+        # alignment needs the acoustic model only: no search, no LM
+        init_adadelta = self.config['hparas']['optimizer'] == 'Adadelta'
+        self.model = test_asr.ASR(self.feat_dim, self.vocab_size, init_adadelta,
+                                  **self.config['model']).to(self.device)
+        self.load_ckpt()        # eval mode
+
     def exec(self):
+        if getattr(self, 'align', False):      # (a solver assembled without __init__ decodes)
+            return align_asr.run(self)
         group = max(1, int(os.environ.get('ASRK_DECODE_BATCH', '16')))
         if self.greedy or not self.ctc_only or not self.decoder.apply_lm or group == 1:
             return super().exec()

@@ -393,6 +393,276 @@ extern "C" int asrk_ctc_loss_bwd_f32(const float *lp, int64_t stride_t, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// CTC forced alignment: the best (Viterbi) path of every utterance through its blank-extended label
+// sequence.  The walk is ctc_lattice_kernel's alpha walk (one wave per utterance, states s = lane*spl + j,
+// previous row in LDS, the next CTC_PF gathered rows in registers) with max in place of lse3:
+//     delta_t[s] = max(delta_{t-1}[s], delta_{t-1}[s-1], delta_{t-1}[s-2] if skip_ok) + lp_t[ext[s]]
+// plain f32 compares and one add, so a host f32 computation in the same order gives the same bits.  Ties
+// take the smallest jump (a candidate replaces the best only if strictly greater, tried 0, 1, 2).
+// Backpointers: jump 0..2 of every state and frame, stored as bit planes - for frame t and register slot
+// j two 64-bit lane masks (__ballot of the jump's low and high bit), i.e. 2 bits per state slot and
+// 4*spl 32-bit words per frame, written by lane 0 - either into LDS behind the two lattice rows or into the
+// caller's workspace.  The backtrace runs in the same launch: lane 0 follows the chain (one dependent 16-byte
+// read per frame) and stores the state of every frame; then all lanes derive tokens and spans from the states.
+namespace {
+
+struct AlignArgs {
+    CtcArgs c;            // lp, lengths, targets, lpg (alpha / beta / nll unused)
+    int32_t *states;      // [B, T]
+    int32_t *tokens;      // [B, T]
+    int32_t *spans;       // [B, Lmax, 2]
+    float *score;         // [B]
+    uint64_t *bp;         // global route: [B, T, spl, 2]
+    int64_t *stamps;      // optional [B, 4]: wall_clock64 at start / lattice done / backtrace done / end
+};
+
+constexpr size_t ALIGN_LDS_BP_BUDGET = 128 * 1024;   // bytes of LDS backpointers per utterance (+ <= 16 KiB rows)
+
+struct alignas(16) BpPair { uint64_t lo, hi; };
+
+static inline size_t align_rows_bytes(int Smax) { return ((size_t)2 * Smax * sizeof(float) + 15) & ~(size_t)15; }
+static inline int align_spl(int Smax) { return (Smax + CTC_THREADS - 1) / CTC_THREADS; }
+static inline size_t align_bp_bytes(int T, int Smax) { return (size_t)T * align_spl(Smax) * sizeof(BpPair); }
+
+template <int SPL, bool BP_LDS>
+__global__ __launch_bounds__(CTC_THREADS) void ctc_viterbi_kernel(AlignArgs a, int rows_bytes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const CtcArgs &p = a.c;
+    float *srow = reinterpret_cast<float *>(smem);   // [2][Smax]
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int Smax = 2 * p.Lmax + 1;
+    const int spl = (Smax + CTC_THREADS - 1) / CTC_THREADS;   // <= SPL
+    const int Tb = min((int)p.in_len[b], p.T);
+    const int tl = max(min((int)p.tg_len[b], p.Lmax), 0);
+    const int S = 2 * tl + 1;
+    const int64_t *tgt = p.targets + (int64_t)b * p.tgt_stride;
+    const float *g = p.lpg + (size_t)b * p.T * Smax;
+    int32_t *st = a.states + (size_t)b * p.T;
+    int32_t *tok = a.tokens + (size_t)b * p.T;
+    int32_t *sp = a.spans + (size_t)b * p.Lmax * 2;
+    BpPair *bp = BP_LDS ? reinterpret_cast<BpPair *>(smem + rows_bytes)
+                        : reinterpret_cast<BpPair *>(a.bp) + (size_t)b * p.T * spl;
+    int64_t *stamp = a.stamps ? a.stamps + (size_t)b * 4 : nullptr;
+    if (stamp && lane == 0) stamp[0] = (int64_t)wall_clock64();
+
+    bool bad = false;     // a target outside [0,V): NaN score like the loss, and nothing is aligned
+    for (int i = lane; i < tl; i += CTC_THREADS) bad |= tgt[i] < 0 || tgt[i] >= p.V;
+    bad = __any(bad);
+
+    float score = bad ? __builtin_nanf("") : (tl == 0 ? 0.f : -INFINITY);   // value when there is no frame
+    int sfin = 0;
+    if (!bad && Tb > 0) {
+        // bit j: register slot j holds a state of this utterance / may take the s-2 transition (per-lane bit sets in
+        // one VGPR each: SPL separate lane predicates would cost two SGPRs apiece)
+        unsigned live = 0, skip = 0;
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) {
+            const int s = lane * spl + j;
+            if (j < spl && s < S) {
+                live |= 1u << j;
+                if ((s & 1) && s >= 2 && ext_label(tgt, s, p.blank) != ext_label(tgt, s - 2, p.blank))
+                    skip |= 1u << j;
+            }
+        }
+        float cur[SPL], pre[CTC_PF][SPL];
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) {
+            cur[j] = -INFINITY;
+            const int s = lane * spl + j;
+            if (((live >> j) & 1) && s <= 1) cur[j] = g[s];
+        }
+#pragma unroll
+        for (int d = 0; d < CTC_PF; ++d)
+#pragma unroll
+            for (int j = 0; j < SPL; ++j) {
+                pre[d][j] = 0.f;
+                const int s = lane * spl + j;
+                if (((live >> j) & 1) && 1 + d < Tb) pre[d][j] = g[(size_t)(1 + d) * Smax + s];
+            }
+
+        for (int base = 0; base < Tb; base += CTC_PF) {
+#pragma unroll
+            for (int d = 0; d < CTC_PF; ++d) {
+                const int step = base + d;
+                if (step >= Tb) break;
+                float *row = srow + (step & 1) * Smax;
+#pragma unroll
+                for (int j = 0; j < SPL; ++j) {
+                    const int s = lane * spl + j;
+                    if (j < spl && s < Smax) row[s] = cur[j];
+                }
+                if (step + 1 == Tb) break;
+                float lpn[SPL];
+                const int nx = step + 1 + CTC_PF;
+#pragma unroll
+                for (int j = 0; j < SPL; ++j) {
+                    lpn[j] = pre[d][j];
+                    const int s = lane * spl + j;
+                    if (((live >> j) & 1) && nx < Tb) pre[d][j] = g[(size_t)nx * Smax + s];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < SPL; ++j) {
+                    if (j < spl) {          // uniform over the wave: every lane reaches the ballots
+                        const int s = lane * spl + j;
+                        int jump = 0;
+                        if ((live >> j) & 1) {
+                            float best = row[s];
+                            if (s >= 1) {
+                                const float a1 = row[s - 1];
+                                if (a1 > best) { best = a1; jump = 1; }
+                            }
+                            if ((skip >> j) & 1) {
+                                const float a2 = row[s - 2];
+                                if (a2 > best) { best = a2; jump = 2; }
+                            }
+                            cur[j] = best + lpn[j];
+                        } else {
+                            cur[j] = -INFINITY;
+                        }
+                        const uint64_t lo = __ballot(jump & 1), hi = __ballot(jump & 2);
+                        if (lane == 0) bp[(size_t)(step + 1) * spl + j] = BpPair{lo, hi};
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        {   // final state: S-1 unless delta[S-2] is strictly greater (all lanes read the same two words)
+            const float *row = srow + ((Tb - 1) & 1) * Smax;
+            const float l1 = row[S - 1];
+            const float l2 = S >= 2 ? row[S - 2] : -INFINITY;
+            sfin = S - 1;
+            score = l1;
+            if (l2 > l1) { sfin = S - 2; score = l2; }
+        }
+    }
+    if (stamp && lane == 0) stamp[1] = (int64_t)wall_clock64();
+
+    // a path exists only behind a score above -inf (false for -inf: too few frames for the target or no path of
+    // non-zero probability; false for NaN)
+    const bool ok = !bad && Tb > 0 && score > -INFINITY;
+    if (ok && lane == 0) {
+        int s = sfin;
+        int ln = s / spl, j = s - ln * spl;     // the lane and register slot that own state s
+        for (int t = Tb - 1; t >= 1; --t) {
+            st[t] = s;
+            const BpPair w = bp[(size_t)t * spl + j];
+            const int jump = (int)((w.lo >> ln) & 1) | ((int)((w.hi >> ln) & 1) << 1);
+            s -= jump;
+            j -= jump;
+            if (j < 0) { j += spl; --ln; }
+            if (j < 0) { j += spl; --ln; }      // spl == 1 and a jump of 2
+            if (s < 0) { s = 0; ln = 0; j = 0; }   // cannot happen behind a finite score; keeps every read in bounds
+        }
+        st[0] = s;
+    }
+    __syncthreads();    // the states lane 0 stored are visible to the whole wave
+    if (stamp && lane == 0) stamp[2] = (int64_t)wall_clock64();
+
+    const int Tv = ok ? Tb : 0, Lv = ok ? tl : 0;
+    for (int t = lane; t < p.T; t += CTC_THREADS) {
+        if (t >= Tv) {
+            st[t] = -1;
+            tok[t] = -1;
+            continue;
+        }
+        const int s = st[t];
+        tok[t] = ext_label(tgt, s, p.blank);
+        if (s & 1) {      // every target token owns one run of frames
+            if (t == 0 || st[t - 1] != s) sp[s - 1] = t;               // spans[s >> 1][0]
+            if (t == Tv - 1 || st[t + 1] != s) sp[s] = t + 1;          // spans[s >> 1][1]
+        }
+    }
+    for (int i = 2 * Lv + lane; i < 2 * p.Lmax; i += CTC_THREADS) sp[i] = -1;
+    if (lane == 0) {
+        a.score[b] = score;
+        if (stamp) stamp[3] = (int64_t)wall_clock64();
+    }
+}
+
+// 0 = bad flags / shape, else ASRK_ALIGN_BP_LDS or ASRK_ALIGN_BP_GLOBAL
+static int align_route(int T, int Smax, int flags) {
+    const bool fits = align_bp_bytes(T, Smax) <= ALIGN_LDS_BP_BUDGET;
+    if (flags == ASRK_ALIGN_BP_AUTO) return fits ? ASRK_ALIGN_BP_LDS : ASRK_ALIGN_BP_GLOBAL;
+    if (flags == ASRK_ALIGN_BP_LDS) return fits ? ASRK_ALIGN_BP_LDS : 0;
+    return flags == ASRK_ALIGN_BP_GLOBAL ? ASRK_ALIGN_BP_GLOBAL : 0;
+}
+
+static inline size_t align_lpg_bytes(int B, int T, int Smax) {
+    return ((size_t)B * T * Smax * sizeof(float) + 15) & ~(size_t)15;
+}
+
+template <int SPL, bool BP_LDS>
+static int align_launch(const AlignArgs &a, int B, size_t rows_bytes, size_t lds, hipStream_t s) {
+    static AsrkLdsLatch latch;
+    if (BP_LDS)
+        ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(ctc_viterbi_kernel<SPL, BP_LDS>),
+                               (int)(align_rows_bytes(CTC_THREADS * CTC_MAX_SPL) + ALIGN_LDS_BP_BUDGET)));
+    hipLaunchKernelGGL((ctc_viterbi_kernel<SPL, BP_LDS>), dim3(B), dim3(CTC_THREADS), lds, s, a, (int)rows_bytes);
+    return ASRK_OK;
+}
+
+}  // namespace
+
+extern "C" size_t asrk_ctc_align_ws_bytes(int B, int T, int Lmax, int flags) {
+    if (B <= 0 || T <= 0 || Lmax < 0 || Lmax > (CTC_THREADS * CTC_MAX_SPL - 1) / 2) return 0;
+    const int Smax = 2 * Lmax + 1;
+    const int route = align_route(T, Smax, flags);
+    if (!route) return 0;
+    return align_lpg_bytes(B, T, Smax) + (route == ASRK_ALIGN_BP_GLOBAL ? (size_t)B * align_bp_bytes(T, Smax) : 0);
+}
+
+extern "C" int asrk_ctc_align_f32(const float *lp, int64_t stride_t, int64_t stride_b, int T, int B, int V,
+                                  const int64_t *targets, int64_t tgt_stride, int Lmax,
+                                  const int64_t *input_lengths, const int64_t *target_lengths, int blank,
+                                  int flags, int32_t *states, int32_t *tokens, int32_t *spans, float *score,
+                                  int64_t *stamps, void *ws, size_t ws_bytes, void *stream) {
+    if (T < 0 || B < 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return ASRK_EINVAL;
+    if (flags != ASRK_ALIGN_BP_AUTO && flags != ASRK_ALIGN_BP_LDS && flags != ASRK_ALIGN_BP_GLOBAL)
+        return ASRK_EINVAL;
+    if (B == 0) return ASRK_OK;
+    if (!input_lengths || !target_lengths || !score) return ASRK_EINVAL;
+    if (T > 0 && (!lp || !states || !tokens)) return ASRK_EINVAL;
+    if (Lmax > 0 && (!targets || !spans)) return ASRK_EINVAL;
+    const int Smax = 2 * Lmax + 1;
+    if (Smax > CTC_THREADS * CTC_MAX_SPL) return ASRK_ESHAPE;
+    const int route = align_route(T, Smax, flags);
+    if (!route) return ASRK_ESHAPE;       // a forced LDS route whose backpointers do not fit the budget
+    const size_t lpg_bytes = align_lpg_bytes(B, T, Smax);
+    const size_t need = lpg_bytes + (route == ASRK_ALIGN_BP_GLOBAL ? (size_t)B * align_bp_bytes(T, Smax) : 0);
+    if (need > 0 && (!ws || ((uintptr_t)ws & 15))) return ASRK_EINVAL;
+    if (ws_bytes < need) return ASRK_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    AlignArgs a{};
+    a.c = CtcArgs{lp, stride_t, stride_b, T, B, V, targets, tgt_stride, Lmax, input_lengths, target_lengths, blank,
+                  nullptr, nullptr, reinterpret_cast<float *>(ws), nullptr};
+    a.states = states;
+    a.tokens = tokens;
+    a.spans = spans;
+    a.score = score;
+    a.bp = route == ASRK_ALIGN_BP_GLOBAL ? reinterpret_cast<uint64_t *>(static_cast<char *>(ws) + lpg_bytes) : nullptr;
+    a.stamps = stamps;
+    asrk_prof_begin_(PROF_CTC, s);
+    if (T > 0)
+        hipLaunchKernelGGL(ctc_gather_kernel, dim3(B, asrk_div_up(T, GATHER_ROWS)), dim3(256), 0, s, a.c);
+    const size_t rows = align_rows_bytes(Smax);
+    const bool lds_bp = route == ASRK_ALIGN_BP_LDS;
+    const size_t lds = rows + (lds_bp ? align_bp_bytes(T, Smax) : 0);
+    int rc;
+    if (Smax <= CTC_THREADS * 4)
+        rc = lds_bp ? align_launch<4, true>(a, B, rows, lds, s) : align_launch<4, false>(a, B, rows, lds, s);
+    else if (Smax <= CTC_THREADS * 16)
+        rc = lds_bp ? align_launch<16, true>(a, B, rows, lds, s) : align_launch<16, false>(a, B, rows, lds, s);
+    else
+        rc = lds_bp ? align_launch<CTC_MAX_SPL, true>(a, B, rows, lds, s)
+                    : align_launch<CTC_MAX_SPL, false>(a, B, rows, lds, s);
+    asrk_prof_end_(PROF_CTC, s);
+    if (rc != ASRK_OK) return rc;
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // CTC prefix scoring for joint CTC-attention beam search (reference: src/ctc.py:76-116,
 // CTCPrefixScore.cheap_compute — numpy on the host, one hypothesis at a time).  Here ALL
 // (hypothesis, candidate) pairs of a beam step run in one launch: one lane per pair walks the

@@ -4,6 +4,7 @@ PyTorch is used for device memory (caching allocator), the current HIP stream an
 bookkeeping only; every tensor that reaches this module is turned into a raw device pointer and
 handed to a hand-written gfx950 kernel.  Nothing here falls back to ATen math.
 """
+import collections
 import ctypes
 
 import torch
@@ -1316,6 +1317,51 @@ class CTCLoss(torch.nn.Module):
     def forward(self, log_probs, targets, input_lengths, target_lengths):
         return CTCLossFn.apply(log_probs, targets, input_lengths, target_lengths, self.blank,
                                self.reduction)
+
+
+# --------------------------------------------------------------------------- CTC forced alignment
+ALIGN_BP_AUTO, ALIGN_BP_LDS, ALIGN_BP_GLOBAL = 0, 1, 2      # ASRK_ALIGN_BP_* (include/asrk.h), per call
+
+CTCAlignment = collections.namedtuple("CTCAlignment", ["states", "tokens", "spans", "score"])
+
+
+@torch.no_grad()
+def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0, flags=ALIGN_BP_AUTO, stamps=None):
+    """Best CTC path of every utterance (asrk_ctc_align_f32): log_probs [T,B,V] (any (stride_t, stride_b), e.g. the
+    transposed view of a [B,T,V] tensor), targets [B,L] padded, lengths [B] -> CTCAlignment of device tensors:
+    states / tokens int32 [B,T] (-1 beyond an utterance's frames), spans int32 [B,L,2] (first frame, last frame + 1 of
+    every target token; -1 beyond its targets), score f32 [B] (log-probability of the path; -inf and -1 everywhere
+    when the target does not fit the frames).  `flags`: where the backpointers live (ALIGN_BP_*).  `stamps`: optional
+    int64 [B,4] device tensor that receives the kernel's phase clocks."""
+    _require_gpu(log_probs)
+    L = _L()
+    if log_probs.dim() != 3:
+        raise _lib.AsrkError("ctc_align: log_probs must be [T, B, V]")
+    if log_probs.dtype != torch.float32:
+        log_probs = log_probs.float()
+    if log_probs.stride(2) != 1:
+        log_probs = log_probs.contiguous()
+    T, B, V = log_probs.shape
+    dev = log_probs.device
+    targets = torch.as_tensor(targets).to(device=dev, dtype=torch.int64)
+    if targets.dim() != 2:
+        raise _lib.AsrkError("ctc_align: only padded 2-D targets [B, L] are supported")
+    targets = targets.contiguous()
+    il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int64).contiguous()
+    tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int64).contiguous()
+    if targets.shape[0] != B or il.numel() != B or tl.numel() != B:
+        raise _lib.AsrkError("ctc_align: targets / lengths do not match the batch of log_probs")
+    Lmax = targets.shape[1]
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    need = L.asrk_ctc_align_ws_bytes(B, T, Lmax, flags)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+    _lib.check(L.asrk_ctc_align_f32(_p(log_probs), log_probs.stride(0), log_probs.stride(1), T, B, V, _p(targets),
+                                    targets.stride(0), Lmax, _p(il), _p(tl), blank, flags, _p(states), _p(tokens),
+                                    _p(spans), _p(score), _p(stamps), _p(ws), need, _stream()), "ctc_align")
+    return CTCAlignment(states, tokens, spans, score)
 
 
 # --------------------------------------------------------------------------- cross entropy

@@ -67,6 +67,22 @@ class ASR(nn.Module):
                 self.attention.mode, 1 - self.ctc_weight))
         return msg
 
+    @torch.no_grad()
+    def ctc_align(self, audio_feature, feature_len, txt, txt_len, packed=False):
+        ''' Forced alignment of every utterance to its transcript with the CTC head: encoder -> CTC head ->
+            log_softmax -> ops.ctc_align (the best CTC path, found and traced back on the device).  txt [B,L] padded
+            token ids, txt_len [B].  Returns (states [B,T'], tokens [B,T'], spans [B,L,2], score [B], encode_len [B]):
+            frames are ENCODER frames (see ops.ctc_align); frames >= encode_len[b] and tokens >= txt_len[b] hold -1.
+            packed=True (needs encoder.supports_packed()): every utterance is encoded as if alone and unpadded, so
+            the other utterances of the batch and its padding never change an alignment. '''
+        if not self.enable_ctc:
+            raise RuntimeError('ASR.ctc_align needs a CTC head: this model was built with ctc_weight = 0')
+        encode_feature, encode_len = self.encoder(audio_feature, feature_len, packed=packed)
+        ctc_output = ops.log_softmax(ops.linear(encode_feature, self.ctc_layer.weight, self.ctc_layer.bias))
+        # the [T',B,V] view of the [B,T',V] log-probs: the kernel takes the strides, nothing is copied
+        al = ops.ctc_align(ctc_output.transpose(0, 1), txt, encode_len, txt_len, blank=0)
+        return al.states, al.tokens, al.spans, al.score, encode_len
+
     def forward(self, audio_feature, feature_len, decode_step, tf_rate=0.0, teacher=None,
                 emb_decoder=None, get_dec_state=False):
         ''' Same contract as the reference (src/asr.py:72-155): returns

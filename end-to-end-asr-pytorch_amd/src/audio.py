@@ -6,6 +6,7 @@ Same module names, constructor arguments, tensor shapes between stages ([C, D, T
 `torchaudio` is not required: 16-bit PCM wav is read with the stdlib `wave` module
 (torchaudio.load semantics: float32 in [-1, 1), [channel, samples]).
 """
+import inspect
 import math
 import wave as _wave
 
@@ -329,6 +330,11 @@ class ExtractAudioFeature(nn.Module):
         y = extract(waveform, num_mel_bins=self.num_mel_bins, channel=-1,
                     sample_frequency=sample_rate, **self.kwargs)
         return _transpose2d(y).unsqueeze(0).detach()
+
+    def frame_shift_ms(self):
+        ''' milliseconds between two feature frames: the configured value, else the extractor's own default '''
+        extract = kaldi_fbank if self.mode == "fbank" else kaldi_mfcc
+        return float(self.kwargs.get('frame_shift', inspect.signature(extract).parameters['frame_shift'].default))
 
     def extra_repr(self):
         return "mode={}, num_mel_bins={}".format(self.mode, self.num_mel_bins)

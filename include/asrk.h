@@ -808,6 +808,44 @@ int asrk_ctc_loss_bwd_f32(const float *lp, int64_t stride_t, int64_t stride_b, i
                           const float *nll, const float *gscale, float *grad, int64_t g_stride_t,
                           int64_t g_stride_b, void *stream);
 
+/* ---- CTC forced alignment: the best (Viterbi) path of every utterance, found and traced back on the device ----------
+ * lp / strides / targets / lengths / blank as asrk_ctc_loss_fwd_f32 (so a [B,T,V]-backed transposed view needs no
+ * copy).  Over the blank-extended labels ext (S_b = 2*L_b + 1 states), frames t < T_b = min(input_lengths[b], T):
+ *     delta_0[s] = lp_0[ext[s]] for s <= 1 (else -inf)
+ *     delta_t[s] = max(delta_{t-1}[s], delta_{t-1}[s-1], delta_{t-1}[s-2] if s odd and ext[s] != ext[s-2]) + lp_t[ext[s]]
+ * in plain f32 (compares and one add: a host f32 computation in this order gives the same bits).  Tie rule: among equal
+ * maxima the smallest jump wins (a candidate replaces the best only if strictly greater, tried in the order s, s-1,
+ * s-2); the path ends in state S_b-1 unless delta[S_b-2] is strictly greater.
+ * Outputs (device): states [B,T] int32 = extended state of every frame; tokens [B,T] = ext[state] (blank or target
+ * token); both -1 for t >= T_b.  spans [B,Lmax,2] = first frame and last frame + 1 of target token l, -1 for l >= L_b.
+ * score [B] = delta of the final state = log-probability of the best path (0 for T_b <= 0 and L_b == 0).
+ * An utterance without a path of non-zero probability (T_b < L_b + number of adjacent repeats, T_b <= 0 < L_b, or
+ * -inf log-probs on every path) gets score -inf and -1 everywhere; a target outside [0,V) gives a NaN score (the
+ * loss's convention; nothing is read out of bounds) and -1 everywhere.
+ * `flags` (per call) picks where the 2-bit backpointers (jump 0..2 per state and frame) live until the backtrace, which
+ * runs in the same launch (nothing returns to the host):
+ *     ASRK_ALIGN_BP_LDS     in LDS, as bit planes: per frame 4*ceil((2*Lmax+1)/64) 32-bit words (2 bits per state,
+ *                           states rounded up to whole 64-lane slots); needs T * that many words <= 128 KiB,
+ *                           ASRK_ESHAPE otherwise
+ *     ASRK_ALIGN_BP_GLOBAL  in the caller's workspace (any T)
+ *     ASRK_ALIGN_BP_AUTO    LDS when it fits those 128 KiB, else the workspace - the default (0)
+ * ws: caller-owned device memory, 16-byte aligned, at least asrk_ctc_align_ws_bytes(B, T, Lmax, flags) bytes (the
+ * gathered log-probs [B,T,2*Lmax+1] and, on the global route, the backpointers), private to the call until the stream
+ * has passed it; ASRK_EWORKSPACE if smaller.  asrk_ctc_align_ws_bytes returns 0 when the call needs no workspace
+ * (B == 0 or T == 0) and for arguments the call rejects.
+ * stamps: optional (NULL allowed) [B,4] int64, device wall-clock ticks of utterance b's wave at its start, after the
+ * lattice, after the backtrace and at its end (for tools/ctc_align_bench.py).
+ * ASRK_EINVAL: a NULL pointer, negative size, blank outside [0,V) or unknown flags; ASRK_ESHAPE: 2*Lmax+1 > 2048 or
+ * a forced LDS route that does not fit - all checked before any device call.  One wave per utterance. */
+#define ASRK_ALIGN_BP_AUTO 0
+#define ASRK_ALIGN_BP_LDS 1
+#define ASRK_ALIGN_BP_GLOBAL 2
+size_t asrk_ctc_align_ws_bytes(int B, int T, int Lmax, int flags);
+int asrk_ctc_align_f32(const float *lp, int64_t stride_t, int64_t stride_b, int T, int B, int V,
+                       const int64_t *targets, int64_t tgt_stride, int Lmax, const int64_t *input_lengths,
+                       const int64_t *target_lengths, int blank, int flags, int32_t *states, int32_t *tokens,
+                       int32_t *spans, float *score, int64_t *stamps, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- CTC prefix scores for joint CTC-attention beam search (src/ctc.py:76-116) -----------
  * All (hypothesis h, candidate c) pairs of one beam step in one launch.  x [T,V] log-probs;
  * r_prev [n,T,2] (0 = non-blank, 1 = blank path) of each hypothesis' prefix g_h; prefix_len[h] =
