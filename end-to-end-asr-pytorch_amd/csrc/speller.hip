@@ -632,6 +632,11 @@ __global__ __launch_bounds__(512) void attend_energy_kernel(AttArgs p) {
     }
 }
 
+// i = a * K + k  ->  a, for i < 2^28, by a multiplication with the rounded-up reciprocal 2^32 / K.  K == 1 has no such
+// 32-bit constant (0xFFFFFFFF / 1 + 1 wraps to 0, which would give a = 0, k = i for every i): there a = i.
+__device__ __forceinline__ unsigned kdiv_of(int K) { return K > 1 ? 0xFFFFFFFFu / (unsigned)K + 1u : 0u; }
+__device__ __forceinline__ int div_k(int i, unsigned kdiv) { return kdiv ? (int)__umulhi((unsigned)i, kdiv) : i; }
+
 // F2a, one memory round trip (round 6).  attend_energy_kernel above is a chain of dependent round trips (staging loops,
 // barrier, the location convolution as 160 serial 201-tap sums, barrier, only then the key loads) behind the 5-us
 // launch floor: 15.7 us for ~2 us of arithmetic.  Here every global operand is requested before anything waits
@@ -652,7 +657,7 @@ __global__ __launch_bounds__(512) void attend_energy_kernel2(AttArgs p) {
     float *s_wp = sm;                               // [A*KP]
     float *red_w = s_wp + A * KP + wave * (16 * RED_RS + 16);   // per wave: [16][RED_RS] tile + [16] features
     float *cb_w = red_w + 16 * RED_RS;
-    const unsigned kdiv = 0xFFFFFFFFu / (unsigned)K + 1u;
+    const unsigned kdiv = kdiv_of(K);
     const int bk = p.row_mem ? p.row_mem[b] : b * p.kvb;
     SP_STAMP(0);
 
@@ -695,7 +700,7 @@ __global__ __launch_bounds__(512) void attend_energy_kernel2(AttArgs p) {
     for (int r = 0; r < AE_WPN; ++r) {
         const int i = tid + 512 * r;
         if (i < AK) {
-            const int a = (int)__umulhi((unsigned)i, kdiv), k = i - a * K;
+            const int a = div_k(i, kdiv), k = i - a * K;
             s_wp[a * KP + k] = wpst[r];
         }
     }
@@ -1194,7 +1199,7 @@ __global__ __launch_bounds__(512) void energy_bwd_kernel3(EbArgs p) {
     float *s_du = s_c + p.tpb * KM;         // [tpb][AP]
     float *s_red = s_du + p.tpb * AP;       // [8][16][RED_RS]; afterwards [8][2][AP]
     const long blk = (long)b * TC + chunk;
-    const unsigned kdiv = 0xFFFFFFFFu / (unsigned)K + 1u;   // i / K == umulhi(i, kdiv) for i < 2^28
+    const unsigned kdiv = kdiv_of(K);
 
     SP_STAMP(0);
     // ---- one round trip: everything this workgroup reads from memory
@@ -1258,7 +1263,7 @@ __global__ __launch_bounds__(512) void energy_bwd_kernel3(EbArgs p) {
     for (int r = 0; r < EB_WPN; ++r) {
         const int i = tid + 512 * r;
         if (i < AK) {
-            const int a = (int)__umulhi((unsigned)i, kdiv), k = i - a * K;
+            const int a = div_k(i, kdiv), k = i - a * K;
             s_wp[a * KP + k] = wpst[r];
         }
     }
@@ -1353,7 +1358,7 @@ __global__ __launch_bounds__(512) void energy_bwd_kernel3(EbArgs p) {
     for (int r = 0; r < EB_WPN; ++r) {
         const int i = tid + 512 * r;
         if (i < AK) {
-            const int a = (int)__umulhi((unsigned)i, kdiv), k = i - a * K;
+            const int a = div_k(i, kdiv), k = i - a * K;
             float acc = 0.f;
             for (int tl = 0; tl < nt; ++tl) acc += s_du[tl * AP + a] * s_c[tl * KM + k];
             p.dWp_part[blk * AK + i] = old_wp[r] + acc;
@@ -1794,6 +1799,18 @@ extern "C" int asrk_speller_plan(const asrk_speller_t *d, int *tc_fwd, int *tc_b
     if (rc) return rc;
     if (tc_fwd) *tc_fwd = pl.tc_f;
     if (tc_bwd) *tc_bwd = pl.tc_b;
+    return ASRK_OK;
+}
+
+extern "C" int asrk_speller_plan_info(const asrk_speller_t *d, int *info) {
+    if (!info) return ASRK_EINVAL;
+    int rc = check_dims(d);
+    if (rc) return rc;
+    Plan pl;
+    rc = make_plan(*d, pl);
+    if (rc) return rc;
+    const int v[8] = {pl.ae2_na, pl.ae2_km, pl.eb3_na, pl.eb3_km, pl.tpb_f, pl.tpb_b, pl.KP, d->Dv % 4 == 0};
+    for (int i = 0; i < 8; ++i) info[i] = v[i];
     return ASRK_OK;
 }
 

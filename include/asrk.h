@@ -499,6 +499,12 @@ typedef struct asrk_speller_bwd {
 /* number of frame chunks (workgroups per utterance) the energy kernels will use: sizes the
  * per-workgroup partial buffers above */
 int asrk_speller_plan(const asrk_speller_t *dims, int *tc_fwd, int *tc_bwd);
+/* read-only report of the kernel variants the same plan selects (host only, nothing is launched):
+ * info[8] = {ae2_na, ae2_km, eb3_na, eb3_km, tpb_f, tpb_b, KP, ctx_vec}.  ae2 / eb3 = the <NA, KM> instantiation of
+ * the one-round-trip forward / backward energy kernel, NA == 0: the staged kernel runs; tpb = frames per
+ * workgroup; KP = padded row pitch of Wp in LDS; ctx_vec = Dv % 4 == 0 (vector softmax/context kernel, given a
+ * 16-byte aligned value).  Dot-product plans (att_mode 1) report 0 in the first four slots. */
+int asrk_speller_plan_info(const asrk_speller_t *dims, int *info);
 int asrk_speller_fwd_f32(const asrk_speller_t *p, void *stream);
 int asrk_speller_bwd_f32(const asrk_speller_t *p, const asrk_speller_bwd_t *g, void *stream);
 /* one attention + decoder-cell step outside the training loop (greedy / beam decoding,
