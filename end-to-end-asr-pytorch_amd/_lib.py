@@ -46,6 +46,9 @@ SIGNATURES = {
     "asrk_cross_entropy_fwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
     "asrk_cross_entropy_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp,
                                            c_vp]),
+    "asrk_cross_entropy_ls_fwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_cross_entropy_ls_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_f32, c_vp, c_vp, c_vp,
+                                              c_vp]),
     "asrk_ctc_prefix_score_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                           c_int, c_int, c_int, c_f32, c_vp]),
     "asrk_ctc_prefix_score_multi_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
@@ -175,6 +178,11 @@ SIGNATURES = {
     "asrk_ctc_loss_bwd_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int,
                                       c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                       c_i64, c_vp]),
+    "asrk_ctc_loss_fwd_ex_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int,
+                                         c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "asrk_ctc_loss_bwd_ex_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int,
+                                         c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                         c_i64, c_int, c_vp]),
     "asrk_ctc_align_ws_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "asrk_ctc_align_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_int,
                                    c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

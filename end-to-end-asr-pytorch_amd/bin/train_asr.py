@@ -14,6 +14,7 @@ from ..src.asr import ASR
 from ..src.optim import Optimizer
 from ..src.data import load_dataset
 from ..src.audio import SpecAugment
+from ..src.loss import LossOptions
 from ..src.util import human_format, cal_er
 
 
@@ -60,8 +61,12 @@ class Solver(BaseSolver):
         self.verbose(self.model.create_msg())
         model_paras = [{'params': self.model.parameters()}]
         # Losses (gfx950 kernels behind the torch.nn loss-module surface)
-        self.seq_loss = ops.CrossEntropyLoss(ignore_index=0)
-        self.ctc_loss = ops.CTCLoss(blank=0, zero_infinity=False)
+        # (top-level `loss:` block; absent = plain cross entropy and zero_infinity=False, as ever)
+        opts = LossOptions.from_config(self.config)
+        self.seq_loss = ops.CrossEntropyLoss(ignore_index=0, label_smoothing=opts.label_smoothing)
+        self.ctc_loss = ops.CTCLoss(blank=0, zero_infinity=opts.ctc_zero_infinity)
+        if opts.active:
+            self.verbose(opts.create_msg())
         self.emb_fuse, self.emb_reg = False, False
         self.optimizer = Optimizer(model_paras, **self.config['hparas'])
         self.verbose(self.optimizer.create_msg())
@@ -133,6 +138,13 @@ class Solver(BaseSolver):
                     self.progress('Tr stat | Loss - {:.2f} | Grad. Norm - {:.2f} | {}'
                                   .format(shown_loss.detach().cpu().item(), float(grad_norm), self.timer.show()))
                     self.write_log('loss', {'tr_ctc': ctc_loss, 'tr_att': att_loss})
+                    # zero_infinity: utterances of this step whose transcript did not fit their encoder frames
+                    # (getattr: a torch loss module has no such counter)
+                    n_zeroed = getattr(self.ctc_loss, 'n_infeasible', None)
+                    n_zeroed = int(n_zeroed) if n_zeroed is not None and ctc_loss is not None else 0
+                    if n_zeroed:
+                        self.verbose('CTC zero_infinity : {} utterance(s) zeroed @ step {}'.format(n_zeroed, self.step))
+                        self.write_log('ctc_zeroed', {'tr': n_zeroed})
                     self.write_log('wer', {'tr_att': cal_er(self.tokenizer, att_output, txt),
                                            'tr_ctc': cal_er(self.tokenizer, ctc_output, txt, ctc=True)})
 

@@ -10,6 +10,7 @@ from ..src.lm import RNNLM
 from ..src.optim import Optimizer
 from ..src.data import load_textset
 from ..src.util import human_format
+from ..src.loss import LossOptions
 
 
 class Solver(BaseSolver):
@@ -33,7 +34,13 @@ class Solver(BaseSolver):
     def set_model(self):
         self.model = RNNLM(self.vocab_size, **self.config['model']).to(self.device)
         self.verbose(self.model.create_msg())
-        self.seq_loss = ops.CrossEntropyLoss(ignore_index=0)
+        # training may smooth the labels (top-level `loss:` block); validation never does, so dev entropy,
+        # perplexity and best_ppx.pth mean what they always meant
+        opts = LossOptions.from_config(self.config, ctc=False)
+        self.seq_loss = ops.CrossEntropyLoss(ignore_index=0, label_smoothing=opts.label_smoothing)
+        self.dev_loss = ops.CrossEntropyLoss(ignore_index=0)
+        if opts.active:
+            self.verbose(opts.create_msg())
         self.optimizer = Optimizer(self.model.parameters(), **self.config['hparas'])
         self.verbose(self.optimizer.create_msg())
         self.load_ckpt()
@@ -43,7 +50,7 @@ class Solver(BaseSolver):
         ''' -> (pred, loss to back-propagate, loss as logged: this rank's own token mean, as the reference's) '''
         pred, _ = self.model(txt[:, :-1], txt_len)
         tgt = txt[:, 1:].reshape(-1)
-        loss = self.seq_loss(pred.view(-1, self.vocab_size), tgt)
+        loss = (self.seq_loss if train else self.dev_loss)(pred.view(-1, self.vocab_size), tgt)
         shown = loss.detach()
         if train and getattr(self, 'dp', None) is not None:
             # CrossEntropy(ignore_index=0) is a mean over THIS rank's non-pad targets; the engine averages

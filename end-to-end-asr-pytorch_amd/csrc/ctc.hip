@@ -45,7 +45,22 @@ struct CtcArgs {
     float *beta;   // [B, T, S]  (nullptr: alpha only)
     float *lpg;    // [B, T, S]  gathered log-probs lp[t, b, ext_b[s]]
     float *nll;    // [B]
+    // zero_infinity (asrk_ctc_loss_fwd_ex_f32): loss[b] = nll[b], or 0 where nll[b] == +inf and zero_inf is set; those
+    // utterances are counted in n_inf.  All three stay 0 / NULL for the plain entry point and the aligner.
+    float *loss;   // [B] or nullptr
+    int *n_inf;    // device counter or nullptr
+    int zero_inf;
 };
+
+// nll[b] keeps +inf as the marker the backward tests; a NaN (targets outside [0,V)) is never zeroed
+__device__ __forceinline__ void ctc_store_nll(const CtcArgs &p, int b, float v) {
+    p.nll[b] = v;
+    if (p.loss) {
+        const bool zeroed = p.zero_inf && v == INFINITY;
+        p.loss[b] = zeroed ? 0.f : v;
+        if (zeroed && p.n_inf) atomicAdd(p.n_inf, 1);
+    }
+}
 
 // ext[s]: blank for even s, target[(s-1)/2] for odd s
 __device__ __forceinline__ int ext_label(const int64_t *tgt, int s, int blank) {
@@ -110,7 +125,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(CtcArgs p) {
     }
 
     if (Tb <= 0) {
-        if (!bw && lane == 0) p.nll[b] = (tl == 0) ? 0.f : INFINITY;
+        if (!bw && lane == 0) ctc_store_nll(p, b, (tl == 0) ? 0.f : INFINITY);
         return;
     }
     {   // torch.nn.CTCLoss rejects targets outside [0,V); here the utterance's loss becomes NaN (no
@@ -118,7 +133,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(CtcArgs p) {
         bool bad = false;
         for (int i = lane; i < tl; i += CTC_THREADS) bad |= tgt[i] < 0 || tgt[i] >= p.V;
         if (__any(bad)) {
-            if (!bw && lane == 0) p.nll[b] = __builtin_nanf("");
+            if (!bw && lane == 0) ctc_store_nll(p, b, __builtin_nanf(""));
             return;
         }
     }
@@ -198,25 +213,25 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(CtcArgs p) {
             const float *row = srow + ((Tb - 1) & 1) * Smax;
             const float l1 = row[S - 1];
             const float l2 = S >= 2 ? row[S - 2] : -INFINITY;
-            p.nll[b] = -log_add(l1, l2);
+            ctc_store_nll(p, b, -log_add(l1, l2));
         }
     }
 }
 
-// dense part: grad = exp(lp) * scale (t < T_b) or 0
+// dense part: grad = exp(lp) * scale (t < T_b) or 0; with zero_inf every row of an utterance whose nll is +inf is 0
 __global__ __launch_bounds__(256) void ctc_grad_dense_kernel(const float *__restrict__ lp,
                                                              int64_t st, int64_t sb, int T, int B,
                                                              int V, const int64_t *in_len,
                                                              const float *gscale,
                                                              float *__restrict__ grad, int64_t gst,
-                                                             int64_t gsb) {
+                                                             int64_t gsb, const float *nll, int zero_inf) {
     const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // row = t*B + b
     const int lane = threadIdx.x & 63;
     if (row >= T * B) return;
     const int t = row / B, b = row - t * B;
     const float *x = lp + (int64_t)t * st + (int64_t)b * sb;
     float *g = grad + (int64_t)t * gst + (int64_t)b * gsb;
-    const bool live = t < (int)in_len[b];
+    const bool live = t < (int)in_len[b] && !(zero_inf && nll[b] == INFINITY);
     const float sc = gscale[b];
     const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15) == 0 &&
                      (V % 4 == 0);
@@ -249,11 +264,15 @@ struct CtcFixArgs {
     float *grad;
     int64_t gst, gsb;
     int t_per_block;
+    int zero_inf;
 };
 
 __global__ __launch_bounds__(256) void ctc_grad_fix_kernel(CtcFixArgs p) {
     extern __shared__ int sm_i[];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // zeroed utterance: the dense pass wrote 0 to all of its rows and the label columns stay 0 (nothing is
+    // computed from the +inf, so no inf * 0); the whole workgroup shares b and leaves together
+    if (p.zero_inf && p.nll[b] == INFINITY) return;
     const int Smax = 2 * p.Lmax + 1;
     int *ext = sm_i;                 // [Smax]
     int *nxt = sm_i + Smax;          // [Smax] next state with the same label (or -1)
@@ -330,15 +349,28 @@ extern "C" int asrk_ctc_loss_fwd_f32(const float *lp, int64_t stride_t, int64_t 
                                      int Lmax, const int64_t *input_lengths,
                                      const int64_t *target_lengths, int blank, float *alpha,
                                      float *beta, float *lpg, float *nll, void *stream) {
+    return asrk_ctc_loss_fwd_ex_f32(lp, stride_t, stride_b, T, B, V, targets, tgt_stride, Lmax, input_lengths,
+                                    target_lengths, blank, alpha, beta, lpg, nll, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int asrk_ctc_loss_fwd_ex_f32(const float *lp, int64_t stride_t, int64_t stride_b, int T, int B, int V,
+                                        const int64_t *targets, int64_t tgt_stride, int Lmax,
+                                        const int64_t *input_lengths, const int64_t *target_lengths, int blank,
+                                        float *alpha, float *beta, float *lpg, float *nll, int flags, float *loss,
+                                        int32_t *n_infeasible, void *stream) {
     if (T < 0 || B < 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return ASRK_EINVAL;
+    if (flags & ~ASRK_CTC_ZERO_INFINITY) return ASRK_EINVAL;
+    if ((flags & ASRK_CTC_ZERO_INFINITY) && !loss) return ASRK_EINVAL;
     if (B == 0) return ASRK_OK;
     if (!lp || !input_lengths || !target_lengths || !alpha || !lpg || !nll) return ASRK_EINVAL;
     if (Lmax > 0 && !targets) return ASRK_EINVAL;
     const int Smax = 2 * Lmax + 1;
     if (Smax > CTC_THREADS * CTC_MAX_SPL) return ASRK_ESHAPE;
     hipStream_t s = (hipStream_t)stream;
+    if (loss && n_infeasible) ASRK_HIP(hipMemsetAsync(n_infeasible, 0, sizeof(int32_t), s));
     CtcArgs a{lp, stride_t, stride_b, T, B, V, targets, tgt_stride, Lmax, input_lengths,
-              target_lengths, blank, alpha, beta, lpg, nll};
+              target_lengths, blank, alpha, beta, lpg, nll, loss, loss ? n_infeasible : nullptr,
+              (flags & ASRK_CTC_ZERO_INFINITY) ? 1 : 0};
     asrk_prof_begin_(PROF_CTC, s);
     if (T > 0)
         hipLaunchKernelGGL(ctc_gather_kernel, dim3(B, asrk_div_up(T, GATHER_ROWS)), dim3(256), 0, s, a);
@@ -364,7 +396,20 @@ extern "C" int asrk_ctc_loss_bwd_f32(const float *lp, int64_t stride_t, int64_t 
                                      const float *beta, const float *lpg, const float *nll,
                                      const float *gscale, float *grad, int64_t g_stride_t,
                                      int64_t g_stride_b, void *stream) {
+    return asrk_ctc_loss_bwd_ex_f32(lp, stride_t, stride_b, T, B, V, targets, tgt_stride, Lmax, input_lengths,
+                                    target_lengths, blank, alpha, beta, lpg, nll, gscale, grad, g_stride_t,
+                                    g_stride_b, 0, stream);
+}
+
+extern "C" int asrk_ctc_loss_bwd_ex_f32(const float *lp, int64_t stride_t, int64_t stride_b, int T, int B, int V,
+                                        const int64_t *targets, int64_t tgt_stride, int Lmax,
+                                        const int64_t *input_lengths, const int64_t *target_lengths, int blank,
+                                        const float *alpha, const float *beta, const float *lpg, const float *nll,
+                                        const float *gscale, float *grad, int64_t g_stride_t, int64_t g_stride_b,
+                                        int flags, void *stream) {
     if (T < 0 || B < 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return ASRK_EINVAL;
+    if (flags & ~ASRK_CTC_ZERO_INFINITY) return ASRK_EINVAL;
+    const int zero_inf = (flags & ASRK_CTC_ZERO_INFINITY) ? 1 : 0;
     if (B == 0 || T == 0) return ASRK_OK;
     if (!lp || !input_lengths || !target_lengths || !alpha || !beta || !lpg || !nll || !gscale || !grad)
         return ASRK_EINVAL;
@@ -377,14 +422,14 @@ extern "C" int asrk_ctc_loss_bwd_f32(const float *lp, int64_t stride_t, int64_t 
     asrk_prof_begin_(PROF_CTC, s);
     hipLaunchKernelGGL(ctc_grad_dense_kernel, dim3(asrk_div_up(T * B, 4)), dim3(256), 0, s, lp,
                        stride_t, stride_b, T, B, V, input_lengths, gscale, grad, g_stride_t,
-                       g_stride_b);
+                       g_stride_b, nll, zero_inf);
     int tchunks = asrk_div_up(512, B);
     if (tchunks > asrk_div_up(T, 4)) tchunks = asrk_div_up(T, 4);
     if (tchunks < 1) tchunks = 1;
     const int tpb = asrk_div_up(asrk_div_up(T, tchunks), 4) * 4;
     tchunks = asrk_div_up(T, tpb);
     CtcFixArgs f{T, B, targets, tgt_stride, Lmax, input_lengths, target_lengths, blank, alpha, beta,
-                 lpg, nll, gscale, grad, g_stride_t, g_stride_b, tpb};
+                 lpg, nll, gscale, grad, g_stride_t, g_stride_b, tpb, zero_inf};
     hipLaunchKernelGGL(ctc_grad_fix_kernel, dim3(B, tchunks), dim3(256),
                        (size_t)Smax * (3 * sizeof(int) + 4 * sizeof(float)), s, f);
     asrk_prof_end_(PROF_CTC, s);

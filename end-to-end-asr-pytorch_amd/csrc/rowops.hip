@@ -542,6 +542,128 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float *__restrict__ x
     }
 }
 
+// label-smoothed cross entropy (CrossEntropyLoss(ignore_index, label_smoothing=eps), uniform smoothing, no class
+// weights): loss_r = (1-eps) * (lse_r - x_r[tgt]) + eps * (lse_r - mean(x_r)).  Same two passes over the row as
+// ce_fwd_kernel; the exp pass also adds up the row (one more accumulator per lane).  The kernel knows nothing of eps:
+// sums[2] += lse_r - mean(x_r) over counted rows, and the caller combines sums[0] and sums[2].  A row whose base is
+// 16-byte aligned (V % 4 == 0) is read as 16-B lanes; the choice is per row and wave-uniform.
+__global__ __launch_bounds__(256) void ce_ls_fwd_kernel(const float *__restrict__ x, int rows, int V, int ld,
+                                                        const int64_t *__restrict__ tgt, int ignore_index,
+                                                        float *__restrict__ row_lse, float *__restrict__ row_smooth,
+                                                        float *__restrict__ sums) {
+    const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float *xr = x + (size_t)row * ld;
+    const bool vec = (reinterpret_cast<uintptr_t>(xr) & 15) == 0 && (V % 4 == 0);
+    const int nv = V >> 2;
+    float m = -INFINITY;
+    if (vec) {
+        for (int i = lane; i < nv; i += 64) {
+            const f32x4 v = reinterpret_cast<const f32x4 *>(xr)[i];
+            m = fmaxf(m, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+        }
+    } else {
+        for (int i = lane; i < V; i += 64) m = fmaxf(m, xr[i]);
+    }
+    m = wave_max(m);
+    float s = 0.f, sx = 0.f;
+    if (vec) {
+        for (int i = lane; i < nv; i += 64) {
+            const f32x4 v = reinterpret_cast<const f32x4 *>(xr)[i];
+            s += (expf(v[0] - m) + expf(v[1] - m)) + (expf(v[2] - m) + expf(v[3] - m));
+            sx += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+    } else {
+        for (int i = lane; i < V; i += 64) {
+            const float v = xr[i];
+            s += expf(v - m);
+            sx += v;
+        }
+    }
+    s = wave_sum(s);
+    sx = wave_sum(sx);
+    const float lse = m + logf(s);
+    if (lane == 0) {
+        const float sm = lse - sx / (float)V;
+        row_lse[row] = lse;
+        row_smooth[row] = sm;
+        const int64_t t = tgt[row];
+        if (sums && t != ignore_index && t >= 0 && t < V) {   // sums == nullptr: ce_ls_sum_kernel adds in a fixed order
+            unsafeAtomicAdd(sums, lse - xr[t]);
+            unsafeAtomicAdd(sums + 1, 1.0f);
+            unsafeAtomicAdd(sums + 2, sm);
+        }
+    }
+}
+
+// ce_sum_kernel with the third sum
+__global__ __launch_bounds__(256) void ce_ls_sum_kernel(const float *__restrict__ x, int rows, int V, int ld,
+                                                        const int64_t *__restrict__ tgt, int ignore_index,
+                                                        const float *__restrict__ row_lse,
+                                                        const float *__restrict__ row_smooth, float *__restrict__ sums) {
+    __shared__ float sl[256], sc[256], ss[256];
+    float a = 0.f, c = 0.f, u = 0.f;
+    for (int r = threadIdx.x; r < rows; r += 256) {
+        const int64_t t = tgt[r];
+        if (t != ignore_index && t >= 0 && t < V) {
+            a += row_lse[r] - x[(size_t)r * ld + t];
+            c += 1.f;
+            u += row_smooth[r];
+        }
+    }
+    sl[threadIdx.x] = a;
+    sc[threadIdx.x] = c;
+    ss[threadIdx.x] = u;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            sl[threadIdx.x] += sl[threadIdx.x + o];
+            sc[threadIdx.x] += sc[threadIdx.x + o];
+            ss[threadIdx.x] += ss[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { sums[0] = sl[0]; sums[1] = sc[0]; sums[2] = ss[0]; }
+}
+
+// dlogits = (softmax - (1-eps) * onehot - eps / V) * gscale for counted rows, 0 for ignored rows
+__global__ __launch_bounds__(256) void ce_ls_bwd_kernel(const float *__restrict__ x, int rows, int V, int ld,
+                                                        const int64_t *__restrict__ tgt, int ignore_index,
+                                                        float eps, const float *__restrict__ row_lse,
+                                                        const float *__restrict__ gscale, float *__restrict__ dx) {
+    const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float *xr = x + (size_t)row * ld;
+    float *dr = dx + (size_t)row * ld;
+    const int64_t t = tgt[row];
+    const bool live = (t != ignore_index && t >= 0 && t < V);
+    const float g = live ? gscale[0] : 0.f;
+    const float lse = row_lse[row];
+    const float hit = 1.f - eps, uni = eps / (float)V;
+    const int ti = live ? (int)t : -1;
+    const bool vec = ((reinterpret_cast<uintptr_t>(xr) | reinterpret_cast<uintptr_t>(dr)) & 15) == 0 && (V % 4 == 0);
+    if (vec) {
+        const int nv = V >> 2;
+        for (int i = lane; i < nv; i += 64) {
+            f32x4 o = {0.f, 0.f, 0.f, 0.f};
+            if (live) {
+                const f32x4 v = reinterpret_cast<const f32x4 *>(xr)[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = (expf(v[j] - lse) - (4 * i + j == ti ? hit : 0.f) - uni) * g;
+            }
+            reinterpret_cast<f32x4 *>(dr)[i] = o;
+        }
+    } else {
+        for (int i = lane; i < V; i += 64) {
+            float v = 0.f;
+            if (live) v = (expf(xr[i] - lse) - (i == ti ? hit : 0.f) - uni) * g;
+            dr[i] = v;
+        }
+    }
+}
+
 inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline unsigned grid_for(int64_t n, int block) {
     int64_t g = asrk_div_up64(n, block);
@@ -736,6 +858,43 @@ extern "C" int asrk_cross_entropy_bwd_f32(const float *logits, int rows, int V, 
     asrk_prof_begin_(PROF_ROWOPS, s);
     hipLaunchKernelGGL(ce_bwd_kernel, dim3(asrk_div_up(rows, 4)), dim3(256), 0, s, logits, rows, V, ld,
                        targets, ignore_index, row_lse, gscale, dlogits);
+    asrk_prof_end_(PROF_ROWOPS, s);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+extern "C" int asrk_cross_entropy_ls_fwd_f32(const float *logits, int rows, int V, int ld, const int64_t *targets,
+                                             int ignore_index, float *row_lse, float *row_smooth, float *sums,
+                                             void *stream) {
+    if (rows < 0 || V <= 0 || ld < V) return ASRK_EINVAL;
+    if (!sums) return ASRK_EINVAL;
+    if (rows > 0 && (!logits || !targets || !row_lse || !row_smooth)) return ASRK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    ASRK_HIP(hipMemsetAsync(sums, 0, 3 * sizeof(float), s));
+    if (rows == 0) return ASRK_OK;
+    asrk_prof_begin_(PROF_ROWOPS, s);
+    const bool det = asrk_knobs_().get(asrk_knobs_().deterministic, 0) != 0;
+    hipLaunchKernelGGL(ce_ls_fwd_kernel, dim3(asrk_div_up(rows, 4)), dim3(256), 0, s, logits, rows, V, ld, targets,
+                       ignore_index, row_lse, row_smooth, det ? nullptr : sums);
+    if (det)
+        hipLaunchKernelGGL(ce_ls_sum_kernel, dim3(1), dim3(256), 0, s, logits, rows, V, ld, targets, ignore_index,
+                           row_lse, row_smooth, sums);
+    asrk_prof_end_(PROF_ROWOPS, s);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+extern "C" int asrk_cross_entropy_ls_bwd_f32(const float *logits, int rows, int V, int ld, const int64_t *targets,
+                                             int ignore_index, float label_smoothing, const float *row_lse,
+                                             const float *gscale, float *dlogits, void *stream) {
+    if (rows < 0 || V <= 0 || ld < V) return ASRK_EINVAL;
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return ASRK_EINVAL;   // NaN included
+    if (rows == 0) return ASRK_OK;
+    if (!logits || !targets || !row_lse || !gscale || !dlogits) return ASRK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    asrk_prof_begin_(PROF_ROWOPS, s);
+    hipLaunchKernelGGL(ce_ls_bwd_kernel, dim3(asrk_div_up(rows, 4)), dim3(256), 0, s, logits, rows, V, ld, targets,
+                       ignore_index, label_smoothing, row_lse, gscale, dlogits);
     asrk_prof_end_(PROF_ROWOPS, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;

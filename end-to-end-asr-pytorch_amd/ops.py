@@ -1236,11 +1236,17 @@ def lstm_layer_packed(x_tm, params_f, params_r, lens, pyramid=None):
 
 
 # --------------------------------------------------------------------------- CTC loss
+CTC_ZERO_INFINITY = 1      # ASRK_CTC_ZERO_INFINITY (include/asrk.h)
+
+
 class CTCLossFn(Function):
-    """torch.nn.CTCLoss(blank, reduction='mean') (reference: bin/train_asr.py:49,123-124)."""
+    """torch.nn.CTCLoss(blank, reduction='mean') (reference: bin/train_asr.py:49,123-124).  zero_infinity=True: an
+    utterance with no path through its frames (nll = +inf) contributes loss 0 and an all-zero gradient; 'mean' still
+    divides by all B utterances.  `count_out`: optional int32 device scalar that receives the number zeroed."""
 
     @staticmethod
-    def forward(ctx, log_probs, targets, input_lengths, target_lengths, blank, reduction):
+    def forward(ctx, log_probs, targets, input_lengths, target_lengths, blank, reduction, zero_infinity=False,
+                count_out=None):
         _require_gpu(log_probs)
         L = _L()
         if log_probs.dtype != torch.float32:
@@ -1263,23 +1269,34 @@ class CTCLossFn(Function):
         # training: the beta lattice runs concurrently with alpha in the same launch
         beta = torch.empty((B, T, S), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         nll = torch.empty((B,), dtype=torch.float32, device=dev)
-        _lib.check(L.asrk_ctc_loss_fwd_f32(_p(log_probs), log_probs.stride(0), log_probs.stride(1), T,
-                                           B, V, _p(targets), targets.stride(0), Lmax, _p(il),
-                                           _p(tl), blank, _p(alpha), _p(beta), _p(lpg), _p(nll),
-                                           _stream()), "ctc_fwd")
+        if zero_infinity:
+            # nll keeps +inf as the marker for the backward; `loss` is what the caller sees
+            loss = torch.empty((B,), dtype=torch.float32, device=dev)
+            if count_out is not None and B == 0:
+                count_out.zero_()
+            _lib.check(L.asrk_ctc_loss_fwd_ex_f32(_p(log_probs), log_probs.stride(0), log_probs.stride(1), T,
+                                                  B, V, _p(targets), targets.stride(0), Lmax, _p(il),
+                                                  _p(tl), blank, _p(alpha), _p(beta), _p(lpg), _p(nll),
+                                                  CTC_ZERO_INFINITY, _p(loss), _p(count_out), _stream()), "ctc_fwd")
+        else:
+            loss = nll
+            _lib.check(L.asrk_ctc_loss_fwd_f32(_p(log_probs), log_probs.stride(0), log_probs.stride(1), T,
+                                               B, V, _p(targets), targets.stride(0), Lmax, _p(il),
+                                               _p(tl), blank, _p(alpha), _p(beta), _p(lpg), _p(nll),
+                                               _stream()), "ctc_fwd")
         ctx.save_for_backward(log_probs, targets, il, tl, alpha, beta, lpg, nll)
-        ctx.meta = (T, B, V, Lmax, blank, reduction)
+        ctx.meta = (T, B, V, Lmax, blank, reduction, bool(zero_infinity))
         if reduction == "mean":
-            return (nll / tl.clamp(min=1).to(torch.float32)).mean()
+            return (loss / tl.clamp(min=1).to(torch.float32)).mean()
         if reduction == "sum":
-            return nll.sum()
-        return nll
+            return loss.sum()
+        return loss
 
     @staticmethod
     def backward(ctx, gout):
         L = _L()
         log_probs, targets, il, tl, alpha, beta, lpg, nll = ctx.saved_tensors
-        T, B, V, Lmax, blank, reduction = ctx.meta
+        T, B, V, Lmax, blank, reduction, zero_infinity = ctx.meta
         dev = log_probs.device
         if reduction == "mean":
             gscale = gout.to(torch.float32) / (tl.clamp(min=1).to(torch.float32) * B)
@@ -1295,28 +1312,43 @@ class CTCLossFn(Function):
             grad = torch.empty((B, T, V), dtype=torch.float32, device=dev).transpose(0, 1)
         else:
             grad = torch.empty((T, B, V), dtype=torch.float32, device=dev)
-        _lib.check(L.asrk_ctc_loss_bwd_f32(_p(log_probs), log_probs.stride(0), log_probs.stride(1), T,
-                                           B, V, _p(targets), targets.stride(0), Lmax, _p(il),
-                                           _p(tl), blank, _p(alpha), _p(beta), _p(lpg), _p(nll), _p(gscale),
-                                           _p(grad), grad.stride(0), grad.stride(1), _stream()),
-                   "ctc_bwd")
-        return grad, None, None, None, None, None
+        if zero_infinity:
+            _lib.check(L.asrk_ctc_loss_bwd_ex_f32(_p(log_probs), log_probs.stride(0), log_probs.stride(1), T,
+                                                  B, V, _p(targets), targets.stride(0), Lmax, _p(il),
+                                                  _p(tl), blank, _p(alpha), _p(beta), _p(lpg), _p(nll), _p(gscale),
+                                                  _p(grad), grad.stride(0), grad.stride(1), CTC_ZERO_INFINITY,
+                                                  _stream()), "ctc_bwd")
+        else:
+            _lib.check(L.asrk_ctc_loss_bwd_f32(_p(log_probs), log_probs.stride(0), log_probs.stride(1), T,
+                                               B, V, _p(targets), targets.stride(0), Lmax, _p(il),
+                                               _p(tl), blank, _p(alpha), _p(beta), _p(lpg), _p(nll), _p(gscale),
+                                               _p(grad), grad.stride(0), grad.stride(1), _stream()),
+                       "ctc_bwd")
+        return grad, None, None, None, None, None, None, None
 
 
 class CTCLoss(torch.nn.Module):
-    """Drop-in for torch.nn.CTCLoss(blank=0, zero_infinity=False) on the MI355X path."""
+    """Drop-in for torch.nn.CTCLoss(blank=0, zero_infinity=...) on the MI355X path.  After a forward with
+    zero_infinity=True, `n_infeasible` is an int32 device scalar: the number of utterances whose loss was zeroed
+    (reading it is the caller's synchronisation, the forward does none)."""
 
     def __init__(self, blank=0, reduction="mean", zero_infinity=False):
         super().__init__()
-        if zero_infinity:
-            raise NotImplementedError("zero_infinity=True is not used by the reference "
-                                      "(bin/train_asr.py:49)")
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError("CTCLoss: unknown reduction %r" % (reduction,))
         self.blank = blank
         self.reduction = reduction
+        self.zero_infinity = bool(zero_infinity)
+        self.n_infeasible = None
 
     def forward(self, log_probs, targets, input_lengths, target_lengths):
+        if not self.zero_infinity:
+            return CTCLossFn.apply(log_probs, targets, input_lengths, target_lengths, self.blank,
+                                   self.reduction)
+        _require_gpu(log_probs)
+        self.n_infeasible = torch.empty((), dtype=torch.int32, device=log_probs.device)
         return CTCLossFn.apply(log_probs, targets, input_lengths, target_lengths, self.blank,
-                               self.reduction)
+                               self.reduction, True, self.n_infeasible)
 
 
 # --------------------------------------------------------------------------- CTC forced alignment
@@ -1365,23 +1397,38 @@ def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0, flags=
 
 
 # --------------------------------------------------------------------------- cross entropy
+def _check_label_smoothing(eps):
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:
+        raise ValueError("label_smoothing must be a number in [0, 1), got %r" % (eps,))
+    return float(eps)
+
+
 class CrossEntropyFn(Function):
     """CrossEntropyLoss(ignore_index, reduction='mean') on logits [R,V], targets [R]
     (reference: bin/train_asr.py:47,130-131)."""
 
     @staticmethod
-    def forward(ctx, logits, targets, ignore_index):
+    def forward(ctx, logits, targets, ignore_index, label_smoothing=0.0):
         _require_gpu(logits)
+        eps = _check_label_smoothing(label_smoothing)
         x = _f32c(logits)
         R, V = x.shape
         tg = targets.to(device=x.device, dtype=torch.int64).contiguous()
         lse = torch.empty((R,), dtype=torch.float32, device=x.device)
-        sums = torch.empty((2,), dtype=torch.float32, device=x.device)
-        _lib.check(_L().asrk_cross_entropy_fwd_f32(_p(x), R, V, V, _p(tg), ignore_index, _p(lse),
-                                                   _p(sums), _stream()), "cross_entropy")
-        ctx.save_for_backward(x, tg, lse, sums)
         ctx.ignore_index = ignore_index
-        return sums[0] / sums[1]
+        ctx.label_smoothing = eps
+        if eps == 0.0:      # the plain kernels: bit-identical to a caller that never heard of smoothing
+            sums = torch.empty((2,), dtype=torch.float32, device=x.device)
+            _lib.check(_L().asrk_cross_entropy_fwd_f32(_p(x), R, V, V, _p(tg), ignore_index, _p(lse),
+                                                       _p(sums), _stream()), "cross_entropy")
+            ctx.save_for_backward(x, tg, lse, sums)
+            return sums[0] / sums[1]
+        smooth = torch.empty((R,), dtype=torch.float32, device=x.device)
+        sums = torch.empty((3,), dtype=torch.float32, device=x.device)     # sum nll, count, sum (lse - mean x)
+        _lib.check(_L().asrk_cross_entropy_ls_fwd_f32(_p(x), R, V, V, _p(tg), ignore_index, _p(lse), _p(smooth),
+                                                      _p(sums), _stream()), "cross_entropy_ls")
+        ctx.save_for_backward(x, tg, lse, sums)
+        return ((1.0 - eps) * sums[0] + eps * sums[2]) / sums[1]
 
     @staticmethod
     def backward(ctx, gout):
@@ -1389,21 +1436,30 @@ class CrossEntropyFn(Function):
         R, V = x.shape
         gscale = (gout.to(torch.float32) / sums[1]).reshape(1).contiguous()
         dx = torch.empty_like(x)
-        _lib.check(_L().asrk_cross_entropy_bwd_f32(_p(x), R, V, V, _p(tg), ctx.ignore_index, _p(lse),
-                                                   _p(gscale), _p(dx), _stream()), "cross_entropy_bwd")
-        return dx, None, None
+        if ctx.label_smoothing == 0.0:
+            _lib.check(_L().asrk_cross_entropy_bwd_f32(_p(x), R, V, V, _p(tg), ctx.ignore_index, _p(lse),
+                                                       _p(gscale), _p(dx), _stream()), "cross_entropy_bwd")
+        else:
+            _lib.check(_L().asrk_cross_entropy_ls_bwd_f32(_p(x), R, V, V, _p(tg), ctx.ignore_index,
+                                                          ctx.label_smoothing, _p(lse), _p(gscale), _p(dx),
+                                                          _stream()), "cross_entropy_ls_bwd")
+        return dx, None, None, None
 
 
 class CrossEntropyLoss(torch.nn.Module):
-    """Drop-in for torch.nn.CrossEntropyLoss(ignore_index=0) on the MI355X path."""
+    """Drop-in for torch.nn.CrossEntropyLoss(ignore_index=0, label_smoothing=...) on the MI355X path (uniform
+    smoothing, no class weights)."""
 
-    def __init__(self, ignore_index=-100, reduction="mean"):
+    def __init__(self, ignore_index=-100, reduction="mean", label_smoothing=0.0):
         super().__init__()
         assert reduction == "mean"
         self.ignore_index = ignore_index
+        self.label_smoothing = _check_label_smoothing(label_smoothing)
 
     def forward(self, logits, targets):
-        return CrossEntropyFn.apply(logits, targets, self.ignore_index)
+        if self.label_smoothing == 0.0:
+            return CrossEntropyFn.apply(logits, targets, self.ignore_index)
+        return CrossEntropyFn.apply(logits, targets, self.ignore_index, self.label_smoothing)
 
 
 # --------------------------------------------------------------------------- LayerNorm / dropout

@@ -194,6 +194,22 @@ int asrk_cross_entropy_bwd_f32(const float *logits, int rows, int V, int ld,
                                const int64_t *targets, int ignore_index, const float *row_lse,
                                const float *gscale, float *dlogits, void *stream);
 
+/* ---- label-smoothed cross entropy: torch.nn.functional.cross_entropy(ignore_index, label_smoothing=eps), uniform
+ * smoothing, no class weights.  Per counted row (tgt != ignore_index and 0 <= tgt < V), lse = logsumexp(logits[r,:]):
+ *     loss_r = (1 - eps) * (lse - logit[tgt]) + eps * (lse - mean(logits[r,:]))
+ * fwd reads the logits as often as asrk_cross_entropy_fwd_f32 and does not take eps: sums[0] and sums[1] as above,
+ *      sums[2] = sum over counted rows of (lse - mean); mean loss = ((1-eps)*sums[0] + eps*sums[2]) / sums[1].
+ *      row_lse[r] and row_smooth[r] = lse - mean are written for every row (row_smooth is what the fixed-order
+ *      reduction under ASRK_DETERMINISTIC=1 adds up).
+ * bwd: dlogits[r,:] = (softmax(logits[r,:]) - (1-eps)*onehot(tgt[r]) - eps/V) * gscale[0], exactly 0 for ignored rows;
+ *      gscale is a device scalar.  ASRK_EINVAL for label_smoothing outside [0, 1) (NaN included).
+ * Both: ASRK_EINVAL for a NULL pointer, checked before any device call. */
+int asrk_cross_entropy_ls_fwd_f32(const float *logits, int rows, int V, int ld, const int64_t *targets,
+                                  int ignore_index, float *row_lse, float *row_smooth, float *sums, void *stream);
+int asrk_cross_entropy_ls_bwd_f32(const float *logits, int rows, int V, int ld, const int64_t *targets,
+                                  int ignore_index, float label_smoothing, const float *row_lse, const float *gscale,
+                                  float *dlogits, void *stream);
+
 /* ---- bidirectional LSTM recurrence, persistent kernels (src/module.py:131 -> ATen lstm) ----
  * Time-major layout.  G: [T*B, ldg] with ldg = ndir*4H, column = dir*4H + gate*H + unit
  * (gate order i,f,g,o as torch).  On entry G holds X*W_ih^T + b_ih + b_hh; on exit the
@@ -813,6 +829,25 @@ int asrk_ctc_loss_bwd_f32(const float *lp, int64_t stride_t, int64_t stride_b, i
                           int blank, const float *alpha, const float *beta, const float *lpg,
                           const float *nll, const float *gscale, float *grad, int64_t g_stride_t,
                           int64_t g_stride_b, void *stream);
+
+/* The same two calls with flags; asrk_ctc_loss_{fwd,bwd}_f32 are these with flags = 0 (loss, n_infeasible NULL).
+ * ASRK_CTC_ZERO_INFINITY = torch's zero_infinity=True.  An utterance whose targets have no path through its frames
+ * has nll[b] = +inf, and nll keeps that value: it is the marker the backward tests.
+ *   fwd: loss[b] ([B], may be NULL without the flag, required with it) = 0 for those utterances, nll[b] otherwise;
+ *        *n_infeasible (device int32, may be NULL) = how many were zeroed (0 without the flag).
+ *   bwd: every gradient element of those utterances is written as exactly 0, label columns included.
+ * A NaN nll (targets outside [0,V)) stays NaN either way.  The caller's 'mean' still divides by all B utterances.
+ * ASRK_EINVAL for unknown flag bits. */
+#define ASRK_CTC_ZERO_INFINITY 1
+int asrk_ctc_loss_fwd_ex_f32(const float *lp, int64_t stride_t, int64_t stride_b, int T, int B, int V,
+                             const int64_t *targets, int64_t tgt_stride, int Lmax, const int64_t *input_lengths,
+                             const int64_t *target_lengths, int blank, float *alpha, float *beta, float *lpg,
+                             float *nll, int flags, float *loss, int32_t *n_infeasible, void *stream);
+int asrk_ctc_loss_bwd_ex_f32(const float *lp, int64_t stride_t, int64_t stride_b, int T, int B, int V,
+                             const int64_t *targets, int64_t tgt_stride, int Lmax, const int64_t *input_lengths,
+                             const int64_t *target_lengths, int blank, const float *alpha, const float *beta,
+                             const float *lpg, const float *nll, const float *gscale, float *grad,
+                             int64_t g_stride_t, int64_t g_stride_b, int flags, void *stream);
 
 /* ---- CTC forced alignment: the best (Viterbi) path of every utterance, found and traced back on the device ----------
  * lp / strides / targets / lengths / blank as asrk_ctc_loss_fwd_f32 (so a [B,T,V]-backed transposed view needs no
