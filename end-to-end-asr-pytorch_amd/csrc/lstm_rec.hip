@@ -298,28 +298,16 @@ extern "C" void asrk_lstm_set_debug_(void *buf, int steps) {
 
 extern "C" size_t asrk_lstm_ws_bytes(void) { return WS_WORDS * sizeof(unsigned); }
 
+// the three older queries are views of asrk_lstm_plan_info (defined below) at the device's CU count
 extern "C" int asrk_lstm_plan_workgroups(int T, int B, int H, int ndir, int backward, int flags) {
-    if (flags < 0 || T <= 0 || B <= 0 || H <= 0 || (ndir != 1 && ndir != 2) || H % 4 != 0) return 0;
-    const int ncu = asrk_cu_count_();
-    if (ncu <= 0) return 0;
-    if (backward) {
-        BwdPlan pl = plan_bwd(T, B, H, ndir, ncu, flags);
-        return pl.ok ? pl.ndir_l * pl.nbg_l * pl.nwg : 0;
-    }
-    FwdPlan pl = plan_fwd(T, B, H, ndir, ncu, flags);
-    return pl.ok ? pl.ndir_l * pl.nbg_l * pl.nwg : 0;
+    int info[ASRK_LSTM_PLAN_INFO_LEN];
+    return asrk_lstm_plan_info(T, B, H, ndir, backward, flags, 0, info) == ASRK_OK ? info[11] : 0;
 }
 
 extern "C" size_t asrk_lstm_xchg_bytes(int T, int B, int H, int ndir, int backward, int flags) {
-    if (flags < 0 || T <= 0 || B <= 0 || H <= 0 || (ndir != 1 && ndir != 2)) return 0;
-    const int ncu = asrk_cu_count_();
-    if (ncu <= 0) return 0;
-    if (backward) {
-        BwdPlan pl = plan_bwd(T, B, H, ndir, ncu, flags);
-        return pl.ok ? pl.xfloats * 4 : 0;
-    }
-    FwdPlan pl = plan_fwd(T, B, H, ndir, ncu, flags);
-    return pl.ok ? pl.xfloats * 4 : 0;
+    int info[ASRK_LSTM_PLAN_INFO_LEN];
+    if (asrk_lstm_plan_info(T, B, H, ndir, backward, flags, 0, info) != ASRK_OK) return 0;
+    return ((size_t)info[13] << 31) | (size_t)info[12];
 }
 
 extern "C" int asrk_lstm_rec_fwd_f32(float *G, const float *whh_f, const float *whh_r, float *Y,
@@ -350,15 +338,42 @@ extern "C" int asrk_lstm_rec_fwd_pyr_panel_f32(float *G, const float *whh_f, con
 
 // 1 if the launch of this shape runs on the bf16x6 recurrence kernel (the one that can emit panels)
 extern "C" int asrk_lstm_plan_is_bf(int T, int B, int H, int ndir, int backward, int flags) {
-    if (flags < 0 || T <= 0 || B <= 0 || H <= 0 || (ndir != 1 && ndir != 2) || H % 4 != 0) return 0;
-    const int ncu = asrk_cu_count_();
-    if (ncu <= 0) return 0;
+    int info[ASRK_LSTM_PLAN_INFO_LEN];
+    return asrk_lstm_plan_info(T, B, H, ndir, backward, flags, 0, info) == ASRK_OK ? info[0] : 0;
+}
+
+// Which kernel a launch of this shape runs (include/asrk.h): the record plan_fwd / plan_bwd hand the launches, and the
+// rejections of rec_fwd_impl / rec_bwd_impl in their order.  ncu > 0 plans for that many CUs without a device call.
+extern "C" int asrk_lstm_plan_info(int T, int B, int H, int ndir, int backward, int flags, int ncu, int *info) {
+    if (!info || ncu < 0) return ASRK_EINVAL;
+    for (int i = 0; i < ASRK_LSTM_PLAN_INFO_LEN; ++i) info[i] = 0;
+    if (flags < 0) return ASRK_EINVAL;
+    if (T < 0 || B <= 0 || H <= 0 || (ndir != 1 && ndir != 2)) return ASRK_EINVAL;
+    if (T == 0) return ASRK_OK;                       // the launch returns before it plans: launches = 0
+    if (H % 4 != 0) return ASRK_ESHAPE;
+    if (ncu == 0) ncu = asrk_cu_count_();
+    if (ncu <= 0) return ASRK_EDEVICE;
+    int nbg_l, ndir_l, nbg;
+    size_t xbytes;
     if (backward) {
-        BwdPlan pl = plan_bwd(T, B, H, ndir, ncu, flags);
-        return pl.ok && pl.bf ? 1 : 0;
+        const BwdPlan pl = plan_bwd(T, B, H, ndir, ncu, flags);
+        if (!pl.ok) return ASRK_ESHAPE;
+        info[0] = pl.bf; info[1] = pl.UB; info[2] = pl.NT; info[3] = pl.bf ? 0 : pl.RK; info[4] = 0;
+        info[8] = pl.nwg; info[10] = (int)pl.lds;
+        ndir_l = pl.ndir_l; nbg_l = pl.nbg_l; nbg = pl.nbg; xbytes = pl.xfloats * 4;
+    } else {
+        const FwdPlan pl = plan_fwd(T, B, H, ndir, ncu, flags);
+        if (!pl.ok) return ASRK_ESHAPE;
+        info[0] = pl.bf; info[1] = pl.MT; info[2] = pl.NT; info[3] = pl.bf ? H / 128 : pl.KGW; info[4] = pl.db;
+        info[8] = pl.nwg; info[10] = (int)pl.lds;
+        ndir_l = pl.ndir_l; nbg_l = pl.nbg_l; nbg = pl.nbg; xbytes = pl.xfloats * 4;
     }
-    FwdPlan pl = plan_fwd(T, B, H, ndir, ncu, flags);
-    return pl.ok && pl.bf ? 1 : 0;
+    info[5] = ((ndir + ndir_l - 1) / ndir_l) * ((nbg + nbg_l - 1) / nbg_l);
+    info[6] = ndir_l; info[7] = nbg_l; info[9] = nbg;
+    info[11] = ndir_l * nbg_l * info[8];
+    info[12] = (int)(xbytes & 0x7fffffffu); info[13] = (int)(xbytes >> 31);
+    info[14] = ncu;
+    return ASRK_OK;
 }
 
 // Inference form with per-row sequence lengths (include/asrk.h): the batched beam-search encoder.

@@ -241,6 +241,23 @@ size_t asrk_lstm_xchg_bytes(int T, int B, int H, int ndir, int backward, int fla
 /* Workgroups (= CUs, one each) a launch of the persistent kernel occupies for this shape; 0 = shape
  * unsupported.  Lets a caller decide what may usefully run beside it on another stream. */
 int asrk_lstm_plan_workgroups(int T, int B, int H, int ndir, int backward, int flags);
+/* Which kernel a launch of this shape and these flags runs, from the very planner the launches use (tuning knobs
+ * included).  Host only when ncu > 0: plan for a device of `ncu` compute units, no device call; ncu == 0: the current
+ * device's count.  Returns what the launch would: ASRK_EINVAL (bad flags / shape arguments, NULL info), ASRK_ESHAPE
+ * (H % 4 != 0, or no plan), ASRK_EDEVICE (ncu == 0 and no device); T == 0 is ASRK_OK with launches = 0.
+ * info[ASRK_LSTM_PLAN_INFO_LEN]:
+ *   [0] family: 0 = f32 MFMA kernel, 1 = bf16x6 kernel
+ *   [1] forward MT (16-row gate tiles per workgroup; units = 4*MT)   | backward UB (units per workgroup)
+ *   [2] NT (16-row batch tiles per workgroup)
+ *   [3] forward KGW (k-groups per wave: 4, 8, 16; bf16x6 kernel: its KSW = H / 128) | backward RK (register-resident
+ *       k-groups: 0, 32; bf16x6 kernel: 0)
+ *   [4] forward db (1 = partial sums double-buffered by step parity) | backward 0
+ *   [5] launches   [6] directions per launch   [7] batch groups per launch   [8] workgroups per (direction, group)
+ *   [9] batch groups in all   [10] dynamic LDS bytes   [11] workgroups per launch (= asrk_lstm_plan_workgroups)
+ *   [12], [13] exchange-buffer bytes, low 31 bits and the rest (= asrk_lstm_xchg_bytes)   [14] the CU count used
+ * asrk_lstm_plan_workgroups, asrk_lstm_plan_is_bf and asrk_lstm_xchg_bytes are views of this record at ncu == 0. */
+#define ASRK_LSTM_PLAN_INFO_LEN 16
+int asrk_lstm_plan_info(int T, int B, int H, int ndir, int backward, int flags, int ncu, int *info);
 /* xchg_prefilled != 0: the caller has already set every byte of `xchg` to 0xFF (e.g. on another
  * stream, off the critical path) since its last use; otherwise the launch fills it first. */
 int asrk_lstm_rec_fwd_f32(float *G, const float *whh_f, const float *whh_r, float *Y, float *C,
