@@ -521,18 +521,6 @@ __global__ __launch_bounds__(256) void gemm_f32_fast_kernel(GemmArgs p) {
 }
 #undef SGB
 
-template <bool A_KC, bool B_KC>
-int launch_gemm_fast(const GemmArgs &a, int lds_hint_kib, hipStream_t s) {
-    static AsrkLdsLatch latch;
-    auto kern = gemm_f32_fast_kernel<A_KC, B_KC>;
-    const int BG_LDS = std::min(158 * 1024, std::max(GEMM_LDS_BYTES, lds_hint_kib * 1024));
-    ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(kern), 158 * 1024));
-    dim3 grid(a.tiles_m * a.tiles_n, a.splitk, 1);
-    hipLaunchKernelGGL(kern, grid, dim3(256), BG_LDS, s, a);
-    ASRK_LAUNCH_CHECK();
-    return ASRK_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Skinny-M path (M <= 32: decoder steps, beam-search batches, RNN-LM steps).  These GEMMs stream
 // the weight matrix once and are HBM-bound, so the kernel is built around the stream, not the
@@ -728,90 +716,87 @@ __global__ void scale_rows_kernel(float *C, int M, int N, int ldc, float beta) {
     C[(size_t)r * ldc + c] *= beta;
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------
+// The dispatch as ONE planner: every routing decision of asrk_gemm_f32 is taken here, on the host, from the
+// shape, the leading dimensions, the operands' 16-byte alignment, beta, splitk, flags, the knobs and the CU
+// count.  asrk_gemm_f32 launches what the record names; asrk_gemm_plan_info reports it.
+enum { GEMM_SKINNY_NT = 0, GEMM_SKINNY_NN = 1, GEMM_SPLIT = 2, GEMM_FAST = 3, GEMM_GENERIC = 4 };
+enum { PRE_NONE = 0, PRE_MEMSET = 1, PRE_SCALE = 2 };
+enum { ST_OVERWRITE = 0, ST_RMW_BETA = 1, ST_ADD = 2, ST_ATOMIC = 3 };
 
-extern "C" int asrk_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
-                             const float *A, int lda, const float *B, int ldb, float beta,
-                             float *C, int ldc, const float *bias, const float *bias2,
-                             int splitk, int flags, void *ws, size_t ws_bytes, void *stream) {
+struct GemmPlan {
+    int path;
+    bool a_kc, b_kc, vec;
+    int splitk, k_per_split;     // K ranges (after clamping) and the k's of each but the last
+    int gx, gy, gz;              // grid of the f32 kernel (0 on the split path: gemm_split.hip plans its own)
+    int prepass, store;
+    int lds;                     // dynamic LDS bytes
+    int launches;                // 0: nothing to do (M == 0 or N == 0)
+    int ncu;
+    int tiles_m, tiles_n;        // tiled kernels; skinny: tiles_n = slabs
+};
+
+// align: bit 0 = A is 16-byte aligned, bit 1 = B is.  ncu > 0: plan for that CU count, no device call.
+int gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, int ldc, int align, float beta,
+              int splitk, int flags, int ncu, GemmPlan &p) {
+    p = GemmPlan{};
     if (M < 0 || N < 0 || K < 0 || flags < 0) return ASRK_EINVAL;
-    const AsrkKnobs &kn = asrk_knobs_();
-    const int lds_hint = (flags >> 8) & 0xff;
+    if (ncu <= 0) ncu = asrk_cu_count_();
+    p.ncu = ncu > 0 ? ncu : 256;
     if (M == 0 || N == 0) return ASRK_OK;
-    if (!A || !B || !C) return ASRK_EINVAL;
     if (transA && transB) return ASRK_EINVAL;  // TT never occurs on this path
-    hipStream_t s = (hipStream_t)stream;
-    const int prof_id = lds_hint > 80 ? PROF_GEMM_BG : PROF_GEMM;
-    asrk_prof_work_(prof_id, 2.0 * (double)M * (double)N * (double)K);
+    const AsrkKnobs &kn = asrk_knobs_();
     const bool a_kc = !transA, b_kc = transB != 0;
+    p.a_kc = a_kc; p.b_kc = b_kc;
     if (lda < (a_kc ? K : M) || ldb < (b_kc ? K : N) || ldc < N) return ASRK_EINVAL;
+    const bool al_a = (align & 1) != 0, al_b = (align & 2) != 0;
+    const bool deterministic = kn.get(kn.deterministic, 0) != 0;
 
-    {
-        // skinny-M path: weight-streaming kernels (see gemm_skinny_*): NT / NN, 16-B accessible operands
-        auto al16s = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        const bool no_skinny = kn.is_set(kn.gemm_noskinny);
-        const bool nt = a_kc && b_kc, nn = a_kc && !b_kc;
-        if (!no_skinny && M <= 32 && (nt || nn) && K >= 32 && K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 &&
-            al16s(A) && al16s(B) && (nt || (N % 4 == 0 && N >= 4)) && (splitk <= 0 || splitk == 1)) {
-            SkinnyArgs k;
-            k.A = A; k.B = B; k.C = C; k.bias = bias; k.bias2 = bias2;
-            k.M = M; k.N = N; k.K = K; k.lda = lda; k.ldb = ldb; k.ldc = ldc; k.alpha = alpha;
-            k.slabs = asrk_div_up(N, nt ? 32 : 128);
-            const int mblocks = asrk_div_up(M, 32);
-            const int chunk = nt ? 32 : 16;
-            // one block = one slab x one K range, cut 4 ways over its waves.  Enough blocks to keep
-            // every CU streaming (~2 blocks = 8 waves per CU), at least 2 chunks per wave, and at
-            // most 8 K ranges per output element (atomic traffic; measured optimum 4-8)
-            int want = asrk_div_up(2 * (asrk_cu_count_() > 0 ? asrk_cu_count_() : 256), k.slabs * mblocks);
-            int sk = std::max(1, std::min(std::min(want, 8), K / (8 * chunk)));
-            if (splitk == 1 || kn.get(kn.deterministic, 0)) sk = 1;   // deterministic: one K range per output element
-            else if (kn.is_set(kn.skinny_sk)) sk = std::max(1, kn.skinny_sk);
-            k.k_per_split = asrk_div_up(asrk_div_up(K, sk), 4 * chunk) * 4 * chunk;
-            k.splitk = asrk_div_up(K, k.k_per_split);
-            // the kernels accumulate into C: establish beta*C first (unless one K range overwrites it)
-            k.overwrite = (k.splitk == 1 && beta == 0.f) ? 1 : 0;
-            if (k.overwrite) {
-            } else if (beta == 0.f) {
-                ASRK_HIP(hipMemset2DAsync(C, (size_t)ldc * 4, 0, (size_t)N * 4, M, s));
-            } else if (beta != 1.f) {
-                const int64_t n = (int64_t)M * N;
-                hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)asrk_div_up64(n, 256)), dim3(256), 0, s, C, M,
-                                   N, ldc, beta);
-                ASRK_LAUNCH_CHECK();
-            }
-            asrk_prof_begin_(prof_id, s);
-            const dim3 grid(k.slabs, k.splitk, mblocks);
-            if (nt) hipLaunchKernelGGL(gemm_skinny_nt_kernel, grid, dim3(256), 0, s, k);
-            else hipLaunchKernelGGL(gemm_skinny_nn_kernel, grid, dim3(256), 0, s, k);
-            asrk_prof_end_(prof_id, s);
-            ASRK_LAUNCH_CHECK();
-            return ASRK_OK;
+    // skinny-M path: weight-streaming kernels (see gemm_skinny_*): NT / NN, 16-B accessible operands
+    const bool nt = a_kc && b_kc, nn = a_kc && !b_kc;
+    if (!kn.is_set(kn.gemm_noskinny) && M <= 32 && (nt || nn) && K >= 32 && K % 4 == 0 && lda % 4 == 0 &&
+        ldb % 4 == 0 && al_a && al_b && (nt || (N % 4 == 0 && N >= 4)) && (splitk <= 0 || splitk == 1)) {
+        p.path = nt ? GEMM_SKINNY_NT : GEMM_SKINNY_NN;
+        p.vec = true;
+        p.tiles_n = asrk_div_up(N, nt ? 32 : 128);
+        p.tiles_m = asrk_div_up(M, 32);
+        const int chunk = nt ? 32 : 16;
+        // one block = one slab x one K range, cut 4 ways over its waves.  Enough blocks to keep
+        // every CU streaming (~2 blocks = 8 waves per CU), at least 2 chunks per wave, and at
+        // most 8 K ranges per output element (atomic traffic; measured optimum 4-8)
+        const int want = asrk_div_up(2 * p.ncu, p.tiles_n * p.tiles_m);
+        int sk = std::max(1, std::min(std::min(want, 8), K / (8 * chunk)));
+        if (splitk == 1 || deterministic) sk = 1;   // deterministic: one K range per output element
+        else if (kn.is_set(kn.skinny_sk)) sk = std::max(1, kn.skinny_sk);
+        p.k_per_split = asrk_div_up(asrk_div_up(K, sk), 4 * chunk) * 4 * chunk;
+        p.splitk = asrk_div_up(K, p.k_per_split);
+        // the kernels accumulate into C: establish beta*C first (unless one K range overwrites it)
+        if (p.splitk == 1 && beta == 0.f) {
+            p.prepass = PRE_NONE;
+            p.store = ST_OVERWRITE;
+        } else {
+            p.prepass = beta == 0.f ? PRE_MEMSET : beta != 1.f ? PRE_SCALE : PRE_NONE;
+            p.store = p.splitk > 1 ? ST_ATOMIC : ST_ADD;
         }
+        p.gx = p.tiles_n; p.gy = p.splitk; p.gz = p.tiles_m;
+        p.lds = 0;
+        p.launches = 1 + (p.prepass != PRE_NONE);
+        return ASRK_OK;
     }
 
-    if (splitk <= 0) {
-        // big contractions: bf16x6 operand splitting on the bf16 matrix cores (gemm_split.hip)
-        if (asrk_gemm_takes_split(M, N, K, flags)) {
-            // the split panels live in the CALLER's workspace (asrk_gemm_ws_bytes): nothing is allocated here
-            if (!ws || ws_bytes < asrk_gemm_ws_bytes(M, N, K, flags)) return ASRK_EWORKSPACE;
-            if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return ASRK_EINVAL;
-            asrk_prof_begin_(prof_id, s);
-            const int rc = asrk_gemm_split_run_(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias,
-                                                bias2, ws, flags, s);
-            asrk_prof_end_(prof_id, s);
-            asrk_prof_launches_(prof_id, 2);     // the two split passes
-            return rc;
-        }
+    // big contractions: bf16x6 operand splitting on the bf16 matrix cores (gemm_split.hip)
+    if (splitk <= 0 && asrk_gemm_takes_split(M, N, K, flags)) {
+        p.path = GEMM_SPLIT;
+        p.splitk = 1;
+        p.k_per_split = K;
+        p.store = beta != 0.f ? ST_RMW_BETA : ST_OVERWRITE;
+        p.launches = 3;                      // the two split passes and the panel GEMM
+        return ASRK_OK;
     }
 
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.bias2 = bias2;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.alpha = alpha; g.beta = beta;
-    g.dbg = kn.get(kn.gemm_dbg, 0);
-    g.tiles_m = asrk_div_up(M, BM);
-    g.tiles_n = asrk_div_up(N, BN);
-    const int tiles = g.tiles_m * g.tiles_n;
+    p.tiles_m = asrk_div_up(M, BM);
+    p.tiles_n = asrk_div_up(N, BN);
+    const int tiles = p.tiles_m * p.tiles_n;
     const int kiters = asrk_div_up(K, BK);
     if (splitk <= 0) {
         // Wave-quantisation model: the chip runs `slots` = 2 workgroups per CU at a time, so a
@@ -819,8 +804,8 @@ extern "C" int asrk_gemm_f32(int transA, int transB, int M, int N, int K, float 
         // 1/s as long but adds atomic read-modify-write traffic on C.  Pick the s that minimises
         //   rounds(tiles*s)/s * (1 + 3% per extra split),   keeping >= 8 K tiles per split.
         splitk = 1;
-        const int slots = 2 * (asrk_cu_count_() > 0 ? asrk_cu_count_() : 256);
-        const int max_split = kn.get(kn.deterministic, 0) ? 0 : kiters / 8;   // deterministic: no atomic split-K
+        const int slots = 2 * p.ncu;
+        const int max_split = deterministic ? 0 : kiters / 8;   // deterministic: no atomic split-K
         if (max_split >= 2 && tiles < 4 * slots) {
             double best = (double)asrk_div_up(tiles, slots);
             for (int sk = 2; sk <= 64 && sk <= max_split; ++sk) {
@@ -835,42 +820,131 @@ extern "C" int asrk_gemm_f32(int transA, int transB, int M, int N, int K, float 
     }
     if (kiters == 0) {
         splitk = 1;
-        g.k_per_split = BK;
+        p.k_per_split = BK;
     } else {
         if (splitk > kiters) splitk = kiters;
-        g.k_per_split = asrk_div_up(kiters, splitk) * BK;
-        splitk = asrk_div_up(K, g.k_per_split);
+        p.k_per_split = asrk_div_up(kiters, splitk) * BK;
+        splitk = asrk_div_up(K, p.k_per_split);
     }
-    g.splitk = splitk;
-
+    p.splitk = splitk;
     if (splitk > 1) {
         // partials are accumulated with atomics on top of beta*C
-        if (beta == 0.f) {
-            ASRK_HIP(hipMemset2DAsync(C, (size_t)ldc * 4, 0, (size_t)N * 4, M, s));
-        } else if (beta != 1.f) {
-            const int64_t n = (int64_t)M * N;
-            hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)asrk_div_up64(n, 256)),
-                               dim3(256), 0, s, C, M, N, ldc, beta);
-            ASRK_LAUNCH_CHECK();
-        }
-        g.beta = 1.f;
+        p.prepass = beta == 0.f ? PRE_MEMSET : beta != 1.f ? PRE_SCALE : PRE_NONE;
+        p.store = ST_ATOMIC;
+    } else {
+        p.prepass = PRE_NONE;
+        p.store = beta != 0.f ? ST_RMW_BETA : ST_OVERWRITE;
+    }
+    // vector (16-B) global loads need aligned bases, ld % 4 == 0 and the contiguous extent % 4 == 0
+    p.vec = al_a && al_b && (lda % 4 == 0) && (ldb % 4 == 0) && ((a_kc ? K : M) % 4 == 0) &&
+            ((b_kc ? K : N) % 4 == 0);
+    // fast path needs 16-B vector access everywhere plus K >= 4 and (for M/N-contiguous operands)
+    // at least 4 rows to clamp into
+    const bool fast = p.vec && !kn.is_set(kn.gemm_nofast) && K >= 4 && (a_kc || M >= 4) && (b_kc || N >= 4);
+    p.path = fast ? GEMM_FAST : GEMM_GENERIC;
+    const int lds_hint = (flags >> 8) & 0xff;
+    p.lds = fast ? std::min(158 * 1024, std::max(GEMM_LDS_BYTES, lds_hint * 1024)) : GEMM_LDS_BYTES;
+    p.gx = tiles; p.gy = splitk; p.gz = 1;
+    p.launches = 1 + (p.prepass != PRE_NONE);
+    return ASRK_OK;
+}
+
+template <bool A_KC, bool B_KC>
+int launch_gemm_fast(const GemmArgs &a, int lds_bytes, hipStream_t s) {
+    static AsrkLdsLatch latch;
+    auto kern = gemm_f32_fast_kernel<A_KC, B_KC>;
+    ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(kern), 158 * 1024));
+    dim3 grid(a.tiles_m * a.tiles_n, a.splitk, 1);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, s, a);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+}  // namespace
+
+extern "C" int asrk_gemm_plan_info(int transA, int transB, int M, int N, int K, int lda, int ldb, int ldc,
+                                   int align, float beta, int splitk, int flags, int ncu, int *info) {
+    if (!info || ncu < 0) return ASRK_EINVAL;
+    GemmPlan p;
+    const int rc = gemm_plan(transA, transB, M, N, K, lda, ldb, ldc, align, beta, splitk, flags, ncu, p);
+    const int rec[ASRK_GEMM_PLAN_INFO_LEN] = {p.path, p.a_kc, p.b_kc, p.vec, p.splitk, p.k_per_split, p.gx, p.gy,
+                                              p.gz, p.prepass, p.store, p.lds, p.launches, p.ncu, 0, 0};
+    for (int i = 0; i < ASRK_GEMM_PLAN_INFO_LEN; ++i) info[i] = rc == ASRK_OK ? rec[i] : 0;
+    return rc;
+}
+
+extern "C" int asrk_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
+                             const float *A, int lda, const float *B, int ldb, float beta,
+                             float *C, int ldc, const float *bias, const float *bias2,
+                             int splitk, int flags, void *ws, size_t ws_bytes, void *stream) {
+    auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    GemmPlan pl;
+    const int prc = gemm_plan(transA, transB, M, N, K, lda, ldb, ldc, (al16(A) ? 1 : 0) | (al16(B) ? 2 : 0), beta,
+                              splitk, flags, 0, pl);
+    if (prc != ASRK_OK) return prc;
+    if (pl.launches == 0) return ASRK_OK;
+    if (!A || !B || !C) return ASRK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int prof_id = ((flags >> 8) & 0xff) > 80 ? PROF_GEMM_BG : PROF_GEMM;
+    asrk_prof_work_(prof_id, 2.0 * (double)M * (double)N * (double)K);
+
+    if (pl.path == GEMM_SPLIT) {
+        // the split panels live in the CALLER's workspace (asrk_gemm_ws_bytes): nothing is allocated here
+        if (!ws || ws_bytes < asrk_gemm_ws_bytes(M, N, K, flags)) return ASRK_EWORKSPACE;
+        if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return ASRK_EINVAL;
+        asrk_prof_begin_(prof_id, s);
+        const int rc = asrk_gemm_split_run_(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias,
+                                            bias2, ws, flags, s);
+        asrk_prof_end_(prof_id, s);
+        asrk_prof_launches_(prof_id, 2);     // the two split passes
+        return rc;
     }
 
-    // vector (16-B) global loads need aligned bases, ld % 4 == 0 and the contiguous extent % 4 == 0
-    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool vec = al16(A) && al16(B) && (lda % 4 == 0) && (ldb % 4 == 0) &&
-                     ((a_kc ? K : M) % 4 == 0) && ((b_kc ? K : N) % 4 == 0);
+    // the split-K and skinny kernels accumulate into C: establish beta*C first
+    if (pl.prepass == PRE_MEMSET) {
+        ASRK_HIP(hipMemset2DAsync(C, (size_t)ldc * 4, 0, (size_t)N * 4, M, s));
+    } else if (pl.prepass == PRE_SCALE) {
+        const int64_t n = (int64_t)M * N;
+        hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)asrk_div_up64(n, 256)), dim3(256), 0, s, C, M, N, ldc,
+                           beta);
+        ASRK_LAUNCH_CHECK();
+    }
+
+    if (pl.path == GEMM_SKINNY_NT || pl.path == GEMM_SKINNY_NN) {
+        SkinnyArgs k;
+        k.A = A; k.B = B; k.C = C; k.bias = bias; k.bias2 = bias2;
+        k.M = M; k.N = N; k.K = K; k.lda = lda; k.ldb = ldb; k.ldc = ldc; k.alpha = alpha;
+        k.slabs = pl.tiles_n;
+        k.splitk = pl.splitk;
+        k.k_per_split = pl.k_per_split;
+        k.overwrite = pl.store == ST_OVERWRITE ? 1 : 0;
+        asrk_prof_begin_(prof_id, s);
+        const dim3 grid(pl.gx, pl.gy, pl.gz);
+        if (pl.path == GEMM_SKINNY_NT) hipLaunchKernelGGL(gemm_skinny_nt_kernel, grid, dim3(256), 0, s, k);
+        else hipLaunchKernelGGL(gemm_skinny_nn_kernel, grid, dim3(256), 0, s, k);
+        asrk_prof_end_(prof_id, s);
+        ASRK_LAUNCH_CHECK();
+        return ASRK_OK;
+    }
+
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.bias2 = bias2;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.alpha = alpha;
+    g.beta = pl.store == ST_ATOMIC ? 1.f : beta;
+    g.dbg = asrk_knobs_().get(asrk_knobs_().gemm_dbg, 0);
+    g.tiles_m = pl.tiles_m;
+    g.tiles_n = pl.tiles_n;
+    g.splitk = pl.splitk;
+    g.k_per_split = pl.k_per_split;
 
     asrk_prof_begin_(prof_id, s);
     int rc;
-    // fast path needs 16-B vector access everywhere plus K >= 4 and (for M/N-contiguous operands)
-    // at least 4 rows to clamp into
-    const bool no_fast = kn.is_set(kn.gemm_nofast);
-    const bool fast = vec && !no_fast && K >= 4 && (a_kc || M >= 4) && (b_kc || N >= 4);
-    if (fast) {
-        if (a_kc && b_kc) rc = launch_gemm_fast<true, true>(g, lds_hint, s);
-        else if (a_kc && !b_kc) rc = launch_gemm_fast<true, false>(g, lds_hint, s);
-        else rc = launch_gemm_fast<false, false>(g, lds_hint, s);
+    const bool a_kc = pl.a_kc, b_kc = pl.b_kc, vec = pl.vec;
+    if (pl.path == GEMM_FAST) {
+        if (a_kc && b_kc) rc = launch_gemm_fast<true, true>(g, pl.lds, s);
+        else if (a_kc && !b_kc) rc = launch_gemm_fast<true, false>(g, pl.lds, s);
+        else rc = launch_gemm_fast<false, false>(g, pl.lds, s);
         asrk_prof_end_(prof_id, s);
         return rc;
     }
@@ -883,4 +957,3 @@ extern "C" int asrk_gemm_f32(int transA, int transB, int M, int N, int K, float 
     asrk_prof_end_(prof_id, s);
     return rc;
 }
-

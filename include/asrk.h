@@ -107,6 +107,24 @@ size_t asrk_gemm_ws_bytes(int M, int N, int K, int flags);
 /* 1 if asrk_gemm_f32 runs an M x N x K contraction on the split path under `flags` */
 int asrk_gemm_takes_split(int M, int N, int K, int flags);
 
+/* Which kernel asrk_gemm_f32 runs for these arguments, from the very planner the launch uses (knobs included).
+ * `align`: bit 0 = A is 16-byte aligned, bit 1 = B is (the query takes no pointers).  Host only when ncu > 0: plan
+ * for a device of `ncu` compute units, no device call; ncu == 0: the current device's count (256 without one, as
+ * the launch assumes).  Returns what the launch would for the same arguments: ASRK_EINVAL for a negative size or
+ * flags, TT, a leading dimension below the extent (and for NULL info / ncu < 0); M == 0 or N == 0 is ASRK_OK with
+ * launches = 0.
+ * info[ASRK_GEMM_PLAN_INFO_LEN]:
+ *   [0] path: 0 skinny NT, 1 skinny NN, 2 bf16x6 split, 3 fast tiled, 4 generic tiled
+ *   [1] a_kc, [2] b_kc (operand stored K-contiguous)   [3] vec (16-byte global loads)
+ *   [4] K ranges (splitk after clamping)   [5] k per range   [6..8] grid x / y / z (0 on the split path)
+ *   [9] pre-pass establishing beta*C: 0 none, 1 memset, 2 scale_rows
+ *   [10] store form of the epilogue: 0 overwrite, 1 read-modify-write with beta, 2 +=, 3 atomics
+ *   [11] dynamic LDS bytes   [12] launches: the kernel, the pre-pass, on the split path the two split passes and the
+ *        panel GEMM (3; its optional 128x128 tail launch is not counted)   [13] the CU count used */
+#define ASRK_GEMM_PLAN_INFO_LEN 16
+int asrk_gemm_plan_info(int transA, int transB, int M, int N, int K, int lda, int ldb, int ldc, int align,
+                        float beta, int splitk, int flags, int ncu, int *info);
+
 /* Split panels as operands of their own: split an operand ONCE, multiply it several times (the weight
  * gradients dW_ih = dG^T X and dW_hh = dG^T H_prev of an LSTM layer share dG^T; autograd of nn.LSTM,
  * src/module.py:131).  A panel holds the three bf16 planes of a logical [rows][K] operand (K = contraction
