@@ -118,6 +118,18 @@ SIGNATURES = {
                                       c_int, c_int, c_vp]),
     "asrk_embedding_fwd_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     "asrk_embedding_bwd_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    "asrk_emb_fuse_bwd_ws_bytes": (c_sz, [c_int] * 6),
+    "asrk_emb_fuse_fwd_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_f32, c_int, c_int, c_vp,
+                                      c_vp, c_vp]),
+    "asrk_emb_fuse_bwd_f32": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_f32, c_vp, c_int,
+                                      c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "asrk_cos_emb_loss_fwd_f32": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_cos_emb_loss_bwd_f32": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_cos_emb_table_grad_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_vp, c_vp]),
+    "asrk_nll_loss_fwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
+    "asrk_nll_loss_bwd_f32": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "asrk_l2norm_fwd_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp]),
+    "asrk_l2norm_bwd_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp]),
     "asrk_layer_norm_fwd_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp]),
     "asrk_layer_norm_bwd_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                                         c_vp]),

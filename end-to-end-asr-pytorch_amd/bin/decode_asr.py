@@ -8,6 +8,11 @@ ONE LM step over all U x beam rows per frame: `search_device_batch`), so this so
 else - greedy decoding, the joint CTC-attention search, CTC search without an LM, output files, the fan-out over
 ranks - is the parent class's.  `ASRK_DECODE_BATCH=1` still restores one utterance at a time.
 
+A decode config with the reference's `emb:` block (`enable: true`, `fuse > 0`; reference: bin/test_asr.py:65-70) decodes
+with embedding fusion: the plug-in (src/plugin.py) is built before the checkpoint is read, BaseSolver.load_ckpt fills it
+from the checkpoint's `emb_decoder` entry, the parent hands it to the joint beam decoder, and for the greedy pass the model is
+wrapped so that it is called with it; without the block nothing here changes.
+
 The optional key `decode: {align: true}` turns the run into CTC forced alignment of both sets to their reference
 transcripts instead of decoding (bin/align_asr.py); without the key nothing here changes.
 """
@@ -15,6 +20,16 @@ import os
 
 from . import align_asr, test_asr
 from ..parallel import gather_in_order
+
+
+class _FusedGreedy:
+    ''' the acoustic model as the greedy pass calls it, decoding over the plug-in's fused distribution '''
+
+    def __init__(self, model, emb_decoder):
+        self.model, self.emb_decoder = model, emb_decoder
+
+    def __call__(self, feat, feat_len, decode_step):
+        return self.model(feat, feat_len, decode_step, emb_decoder=self.emb_decoder)
 
 
 class Solver(test_asr.Solver):
@@ -34,12 +49,25 @@ class Solver(test_asr.Solver):
 
     def set_model(self):
         if not getattr(self, 'align', False):
-            return super().set_model()
+            super().set_model()
+            if self.greedy and self.emb_decoder is not None:
+                # the parent's greedy pass calls self.decoder(feat, feat_len, steps): the model, with the plug-in bound
+                self.decoder = _FusedGreedy(self.model, self.emb_decoder)
+            return
         # alignment needs the acoustic model only: no search, no LM
         init_adadelta = self.config['hparas']['optimizer'] == 'Adadelta'
         self.model = test_asr.ASR(self.feat_dim, self.vocab_size, init_adadelta,
                                   **self.config['model']).to(self.device)
         self.load_ckpt()        # eval mode
+
+    def load_ckpt(self):
+        ''' the parent's set_model calls this between building the model and building the decoder: the place where the
+            plug-in has to exist (the checkpoint entry is loaded into it, the beam decoder is constructed with it) '''
+        emb = self.config.get('emb')
+        if emb and emb['enable'] and emb['fuse'] > 0 and not getattr(self, 'align', False):
+            from ..src.plugin import EmbeddingRegularizer
+            self.emb_decoder = EmbeddingRegularizer(self.tokenizer, self.model.dec_dim, **emb).to(self.device)
+        super().load_ckpt()     # eval mode, plug-in included
 
     def exec(self):
         if getattr(self, 'align', False):      # (a solver assembled without __init__ decodes)

@@ -26,8 +26,6 @@ class Solver(BaseSolver):
         self.best_wer = {'att': 3.0, 'ctc': 3.0}
         # Curriculum learning affects data loader
         self.curriculum = self.config['hparas']['curriculum']
-        if 'emb' in self.config and self.config['emb']['enable']:
-            raise NotImplementedError('embedding regulariser/fusion plugin (src/plugin.py) is out of scope')
 
     def fetch_data(self, data):
         ''' batch is already resident in HBM (src/data.py); compute text seq. length '''
@@ -67,15 +65,34 @@ class Solver(BaseSolver):
         self.ctc_loss = ops.CTCLoss(blank=0, zero_infinity=opts.ctc_zero_infinity)
         if opts.active:
             self.verbose(opts.create_msg())
-        self.emb_fuse, self.emb_reg = False, False
+        # Plug-ins (reference: bin/train_asr.py:51-63): word-embedding regulariser / embedding-fusion decoder
+        self.emb_fuse = False
+        self.emb_reg = ('emb' in self.config) and bool(self.config['emb']['enable'])
+        if self.emb_reg:
+            if self.world > 1:
+                raise NotImplementedError(
+                    'emb.enable with WORLD_SIZE > 1: the data-parallel engine averages the gradients of the model '
+                    'only, the plug-in\'s parameters would drift apart between ranks; train it on one GPU')
+            from ..src.plugin import EmbeddingRegularizer
+            self.emb_decoder = EmbeddingRegularizer(
+                self.tokenizer, self.model.dec_dim, **self.config['emb']).to(self.device)
+            model_paras.append({'params': self.emb_decoder.parameters()})
+            self.emb_fuse = self.emb_decoder.apply_fuse
+            if self.emb_fuse:
+                if opts.label_smoothing != 0.0:
+                    raise ValueError('loss.label_smoothing with emb.fuse: smoothing is defined on logits, the fused '
+                                     'decoder output is a log-probability; drop one of the two')
+                self.seq_loss = ops.NLLLoss(ignore_index=0)
+            self.verbose(self.emb_decoder.create_msg())
         self.optimizer = Optimizer(model_paras, **self.config['hparas'])
         self.verbose(self.optimizer.create_msg())
         self.load_ckpt()
         self.enable_data_parallel()
 
-    def compute_losses(self, ctc_output, encode_len, att_output, txt, txt_len):
-        ''' (reference: bin/train_asr.py:115-133) -> (loss to back-propagate, ctc_loss, att_loss, total loss as the
-            reference would log it for this rank's batch).
+    def compute_losses(self, ctc_output, encode_len, att_output, txt, txt_len, emb_loss=None):
+        ''' (reference: bin/train_asr.py:108-133) -> (loss to back-propagate, ctc_loss, att_loss, total loss as the
+            reference would log it for this rank's batch).  `att_output` is the fused log-probability under embedding
+            fusion (seq_loss is then the NLL loss); `emb_loss` enters with the plug-in's weight.
 
             Data parallel (one process per GPU, gradients AVERAGED over ranks by parallel.DataParallelEngine): for the
             update to equal the single-process step on the GLOBAL batch (SURVEY §8e cond. 1, 2)
@@ -88,6 +105,9 @@ class Solver(BaseSolver):
             counts = torch.stack([txt_len.new_tensor(txt.shape[0]), txt_len.sum()]).to(torch.float64)
             w = (counts / self.dp.count_normaliser(counts)).to(torch.float32)
             w_ctc, w_att = w[0], w[1]
+        if emb_loss is not None:
+            shown_loss = shown_loss + emb_loss.detach() * self.emb_decoder.weight
+            total_loss += emb_loss * self.emb_decoder.weight
         if ctc_output is not None:
             ctc_loss = self.ctc_loss(ctc_output.transpose(0, 1), txt, encode_len, txt_len)
             shown_loss = shown_loss + ctc_loss.detach() * self.model.ctc_weight
@@ -102,7 +122,7 @@ class Solver(BaseSolver):
     def exec(self):
         ''' Training End-to-end ASR system '''
         self.verbose('Total training steps {}.'.format(human_format(self.max_step)))
-        ctc_loss, att_loss = None, None
+        ctc_loss, att_loss, emb_loss = None, None, None
         n_epochs = 0
         self.timer.set()
         while self.step < self.max_step:
@@ -124,10 +144,19 @@ class Solver(BaseSolver):
                 self.timer.cnt('rd')
 
                 # Note: txt should NOT start w/ <sos>
-                ctc_output, encode_len, att_output, att_align, dec_state = \
-                    self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt)
-                total_loss, ctc_loss, att_loss, shown_loss = \
-                    self.compute_losses(ctc_output, encode_len, att_output, txt, txt_len)
+                if not self.emb_reg:
+                    ctc_output, encode_len, att_output, att_align, dec_state = \
+                        self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt)
+                    total_loss, ctc_loss, att_loss, shown_loss = \
+                        self.compute_losses(ctc_output, encode_len, att_output, txt, txt_len)
+                else:
+                    ctc_output, encode_len, att_output, att_align, dec_state = \
+                        self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt, get_dec_state=True)
+                    emb_loss, fuse_output = self.emb_decoder(dec_state, att_output, label=txt)
+                    if self.emb_fuse:
+                        att_output = fuse_output        # the attention loss and the error rate read the mixture
+                    total_loss, ctc_loss, att_loss, shown_loss = \
+                        self.compute_losses(ctc_output, encode_len, att_output, txt, txt_len, emb_loss=emb_loss)
                 self.timer.cnt('fw')
 
                 grad_norm = self.backward(total_loss)
@@ -138,6 +167,12 @@ class Solver(BaseSolver):
                     self.progress('Tr stat | Loss - {:.2f} | Grad. Norm - {:.2f} | {}'
                                   .format(shown_loss.detach().cpu().item(), float(grad_norm), self.timer.show()))
                     self.write_log('loss', {'tr_ctc': ctc_loss, 'tr_att': att_loss})
+                    if self.emb_reg:
+                        self.write_log('emb_loss', {'tr': emb_loss})
+                        if self.emb_fuse:
+                            if self.emb_decoder.fuse_learnable:
+                                self.write_log('fuse_lambda', {'emb': self.emb_decoder.get_weight()})
+                            self.write_log('fuse_temp', {'temp': self.emb_decoder.get_temp()})
                     # zero_infinity: utterances of this step whose transcript did not fit their encoder frames
                     # (getattr: a torch loss module has no such counter)
                     n_zeroed = getattr(self.ctc_loss, 'n_infeasible', None)
@@ -162,13 +197,20 @@ class Solver(BaseSolver):
     def validate(self):
         self.poll_device_errors(force=True)     # a validation score / checkpoint of parameters that are known good
         self.model.eval()
+        if self.emb_decoder is not None:
+            self.emb_decoder.eval()
         dev_wer = {'att': [], 'ctc': []}
         for i, data in enumerate(self.dv_set):
             self.progress('Valid step - {}/{}'.format(i + 1, len(self.dv_set)))
             feat, feat_len, txt, txt_len = self.fetch_data(data)
             with torch.no_grad():
-                ctc_output, encode_len, att_output, att_align, dec_state = \
-                    self.model(feat, feat_len, int(self.decode_step * self.DEV_STEP_RATIO))
+                if not self.emb_fuse:   # (a regulariser-only plug-in has no say in decoding: the fused greedy loop)
+                    ctc_output, encode_len, att_output, att_align, dec_state = \
+                        self.model(feat, feat_len, int(self.decode_step * self.DEV_STEP_RATIO))
+                else:       # greedy decoding over the fused distribution: the per-step loop of ASR.forward
+                    ctc_output, encode_len, att_output, att_align, dec_state = \
+                        self.model(feat, feat_len, int(self.decode_step * self.DEV_STEP_RATIO),
+                                   emb_decoder=self.emb_decoder)
             dev_wer['att'].append(cal_er(self.tokenizer, att_output, txt))
             dev_wer['ctc'].append(cal_er(self.tokenizer, ctc_output, txt, ctc=True))
 
@@ -193,3 +235,5 @@ class Solver(BaseSolver):
             self.write_log('wer', {'dv_' + task: dev_wer[task]})
         self.save_checkpoint('latest.pth', 'wer', dev_wer['att'], show_msg=False)
         self.model.train()
+        if self.emb_decoder is not None:
+            self.emb_decoder.train()

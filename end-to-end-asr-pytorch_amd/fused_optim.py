@@ -52,15 +52,20 @@ class _FusedMixin:
         raise NotImplementedError
 
     @torch.no_grad()
-    def step(self, closure=None, clip_coef=None):
+    def step(self, closure=None, clip_coef=None, clip_groups=None):
         """clip_coef: optional device scalar max_norm / (total_norm + 1e-6).  All tensors of a
-        param_group go to the device in ONE call (asrk_*_multi_f32)."""
+        param_group go to the device in ONE call (asrk_*_multi_f32).  clip_groups = k: only the first k param_groups
+        are clipped (the reference clips the model's gradients, not a plug-in's: src/solver.py:84); the others take
+        their gradients as they are, but still skip the update when the coefficient is NaN."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         k0, k1 = self._state_keys
-        for group in self.param_groups:
+        unclipped = None
+        if clip_coef is not None and clip_groups is not None and clip_groups < len(self.param_groups):
+            unclipped = clip_coef * 0 + 1        # 1, or NaN with the coefficient: the kernels' skip predicate
+        for gi, group in enumerate(self.param_groups):
             if group.get('weight_decay', 0) != 0 or group.get('maximize', False) or group.get('amsgrad', False):
                 raise NotImplementedError("fused step: weight_decay / maximize / amsgrad are not used by the "
                                           "reference configs")
@@ -84,8 +89,9 @@ class _FusedMixin:
             if not params:
                 continue
             numel = (ctypes.c_int64 * len(params))(*[p.numel() for p in params])
+            coef = clip_coef if (clip_groups is None or gi < clip_groups) else unclipped
             self._launch_group(group, params, _ptr_array(params), _ptr_array(grads), _ptr_array(st0),
-                               _ptr_array(st1), numel, clip_coef)
+                               _ptr_array(st1), numel, coef)
         return loss
 
     def clip_and_step(self, max_norm):

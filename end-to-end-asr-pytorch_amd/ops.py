@@ -1462,6 +1462,47 @@ class CrossEntropyLoss(torch.nn.Module):
         return CrossEntropyFn.apply(logits, targets, self.ignore_index, self.label_smoothing)
 
 
+class NLLLossFn(Function):
+    """NLLLoss(ignore_index, reduction='mean') on log-probabilities [R,V], targets [R] (reference:
+    bin/train_asr.py:62, the attention loss under embedding fusion)."""
+
+    @staticmethod
+    def forward(ctx, logp, targets, ignore_index):
+        _require_gpu(logp)
+        x = _f32c(logp)
+        R, V = x.shape
+        tg = targets.to(device=x.device, dtype=torch.int64).contiguous()
+        if tg.numel() != R:
+            raise RuntimeError("nll_loss: %d targets for %d rows" % (tg.numel(), R))
+        sums = torch.empty((2,), dtype=torch.float32, device=x.device)
+        _lib.check(_L().asrk_nll_loss_fwd_f32(_p(x), R, V, V, _p(tg), ignore_index, _p(sums), _stream()), "nll_loss")
+        ctx.ignore_index, ctx.shape = ignore_index, (R, V)
+        ctx.save_for_backward(tg, sums)
+        return sums[0] / sums[1]
+
+    @staticmethod
+    def backward(ctx, gout):
+        tg, sums = ctx.saved_tensors
+        R, V = ctx.shape
+        gscale = (gout.to(torch.float32) / sums[1]).reshape(1).contiguous()
+        dx = torch.empty((R, V), dtype=torch.float32, device=tg.device)
+        _lib.check(_L().asrk_nll_loss_bwd_f32(R, V, V, _p(tg), ctx.ignore_index, _p(gscale), _p(dx), _stream()),
+                   "nll_loss_bwd")
+        return dx, None, None
+
+
+class NLLLoss(torch.nn.Module):
+    """Drop-in for torch.nn.NLLLoss(ignore_index=0) on the MI355X path (no class weights)."""
+
+    def __init__(self, ignore_index=-100, reduction="mean"):
+        super().__init__()
+        assert reduction == "mean"
+        self.ignore_index = ignore_index
+
+    def forward(self, logp, targets):
+        return NLLLossFn.apply(logp, targets, self.ignore_index)
+
+
 # --------------------------------------------------------------------------- LayerNorm / dropout
 class LayerNormFn(Function):
     """torch.nn.LayerNorm(D) over the last axis (reference: src/module.py:116-117,135-136)."""

@@ -56,7 +56,7 @@ class BeamDecoder(nn.Module):
 
         self.apply_emb = emb_decoder is not None
         if self.apply_emb:
-            raise NotImplementedError('embedding-fusion decoding (src/plugin.py) is out of scope')
+            self.emb_decoder = emb_decoder
 
     def create_msg(self):
         msg = ['Decode spec| Beam size = {}\t| Min/Max len ratio = {}/{}'.format(
@@ -66,7 +66,17 @@ class BeamDecoder(nn.Module):
         if self.apply_lm:
             msg.append('           |Joint LM decoding enabled \t| weight = {:.2f}\t| src = {}'.format(
                 self.lm_w, self.lm_path))
+        if self.apply_emb:
+            msg.append('           |Joint Emb. decoding enabled \t| weight = {:.2f}'.format(
+                self.emb_decoder.fuse_lambda.mean().cpu().item()))
         return msg
+
+    def _att_logp(self, state, logit):
+        ''' log-probabilities of a decode position from the top decoder states [n,D] and the vocabulary logits [n,V]:
+            log-softmax, or the plug-in's mixture with the embedding distribution (src/decode.py:117-121) '''
+        if self.apply_emb:
+            return self.emb_decoder.infer(state, logit)
+        return ops.log_softmax(logit)
 
     @torch.no_grad()
     def forward(self, audio_feature, feature_len):
@@ -86,6 +96,8 @@ class BeamDecoder(nn.Module):
         encode_feature, encode_len = asr.encoder(audio_feature, feature_len)
         T = encode_feature.shape[1]
         att.reset_mem()
+        if self.apply_emb:
+            self.emb_decoder.begin_search()
         # single-head location-aware attention + one-layer LSTM / GRU decoder: one fused C call per step
         # (csrc/speller.hip) over ONE copy of the utterance's key / value for all hypotheses
         fused = sops.supported_loop(att, dec)
@@ -188,7 +200,7 @@ class BeamDecoder(nn.Module):
                     cs.append(cl)
                     x = hl
                 h_new, c_new = torch.stack(hs, 0), torch.stack(cs, 0)
-            att_logp = ops.log_softmax(ops.linear(x, dec.char_trans.weight, dec.char_trans.bias))
+            att_logp = self._att_logp(x, ops.linear(x, dec.char_trans.weight, dec.char_trans.bias))
 
             # ---- CTC prefix scoring on limited candidates (src/decode.py:123-138)
             cand, psi, r_new, prev_ctc = None, None, None, None
@@ -355,6 +367,8 @@ class BeamDecoder(nn.Module):
         plen_all = torch.arange(lmax, **i32).view(lmax, 1).expand(lmax, R).contiguous()   # int32: what the scorer takes
         stepper = sops.MultiSpellerStepper(att, dec, sh['s_key'], sh['s_value'], enc_len_dev, R, row_group=B_)
         dops.drop_weight_panels()                 # weights may have been updated since the last search
+        if self.apply_emb:
+            self.emb_decoder.begin_search()
         p_ = lambda t_: ctypes.c_void_p(t_.data_ptr()) if t_ is not None else ctypes.c_void_p(0)
         h_new = c_new = attn = lm_h = lm_c = r_new = None
         lm_hidden = None
@@ -432,7 +446,7 @@ class BeamDecoder(nn.Module):
             attn, context, x, c_top = stepper.step(row_mem32, dops.embedding(prev_token, asr.pre_embed.weight),
                                                    prev_att, h_in, c_in, state=state)
             h_new, c_new = x, c_top
-            att_logp = ops.log_softmax(dops.linear_infer(x, dec.char_trans.weight, dec.char_trans.bias))
+            att_logp = self._att_logp(x, dops.linear_infer(x, dec.char_trans.weight, dec.char_trans.bias))
             cand, psi, r_new = None, None, None
             if self.apply_ctc:
                 _, cand = ops.topk(att_logp, C)

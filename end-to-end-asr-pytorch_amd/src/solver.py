@@ -111,7 +111,7 @@ class BaseSolver():
             self.exp_name = paras.config.split('/')[-1].replace('.yaml', '')
             if mode == 'train':
                 self.exp_name += '_sd{}'.format(paras.seed)
-        self.emb_decoder = None     # embedding-fusion plugin: out of scope
+        self.emb_decoder = None     # word-embedding plug-in (src/plugin.py); the solvers build it from the `emb:` block
 
         if mode == 'train':
             os.makedirs(paras.ckpdir, exist_ok=True)
@@ -171,16 +171,19 @@ class BaseSolver():
             # clipping is folded into the fused update: the gradients are read once, never rewritten
             from ..fused_optim import grad_norm_and_coef
             grad_norm, coef = grad_norm_and_coef(list(self.model.parameters()), self.GRAD_CLIP)
+            # the reference clips the model's gradients only (src/solver.py:84); the plug-in's parameters (second
+            # parameter group) are stepped with theirs as they are
+            groups = {} if getattr(self, 'emb_decoder', None) is None else {'clip_groups': 1}
             if getattr(self.optimizer, 'device_nan_skip', False):
                 # the update kernel itself leaves parameters and state untouched when the norm is NaN
-                self.optimizer.step(grad_norm, self.GRAD_CLIP, coef=coef)
+                self.optimizer.step(grad_norm, self.GRAD_CLIP, coef=coef, **groups)
                 if not hasattr(self, '_nan_watch'):
                     self._nan_watch = []
                 self._nan_watch.append((self.step, grad_norm))
             elif math.isnan(grad_norm):
                 self.verbose('Error : grad norm is NaN @ step ' + str(self.step))
             else:
-                self.optimizer.step(grad_norm, self.GRAD_CLIP, coef=coef)
+                self.optimizer.step(grad_norm, self.GRAD_CLIP, coef=coef, **groups)
         else:
             grad_norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.GRAD_CLIP)
             if math.isnan(grad_norm):
@@ -195,6 +198,8 @@ class BaseSolver():
         if self.paras.load:
             ckpt = torch.load(self.paras.load, map_location=self.device if self.mode == 'train' else 'cpu')
             self.model.load_state_dict(ckpt['model'])
+            if self.emb_decoder is not None:
+                self.emb_decoder.load_state_dict(ckpt['emb_decoder'])
             metric, score = "None", 0.0
             for k, v in ckpt.items():
                 if type(v) is float:
@@ -206,6 +211,8 @@ class BaseSolver():
                     self.paras.load, self.step, metric, score))
             else:
                 self.model.eval()
+                if self.emb_decoder is not None:
+                    self.emb_decoder.eval()
                 self.verbose('Evaluation target = {} (recorded {} = {:.2f} %)'.format(
                     self.paras.load, metric, score))
 
@@ -253,6 +260,8 @@ class BaseSolver():
             "global_step": self.step,
             metric: score
         }
+        if self.emb_decoder is not None:
+            full_dict['emb_decoder'] = self.emb_decoder.state_dict()
         torch.save(full_dict, ckpt_path)
         if show_msg:
             self.verbose("Saved checkpoint (step = {}, {} = {:.2f}) and status @ {}".

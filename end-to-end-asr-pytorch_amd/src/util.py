@@ -98,6 +98,34 @@ def edit_distance(a, b):
     return prev[-1]
 
 
+def load_embedding(text_encoder, embedding_filepath):
+    """Pretrained word vectors as a float64 [vocab_size, dim] array in the text encoder's index order (reference:
+    src/util.py:130-163).  The file is fastText's text format: a header line `<words> <dim>`, then one
+    `<word> <v_1> ... <v_dim>` line per word.  `</s>` names the encoder's `<eos>`; a word maps to its subword piece id
+    or to the first id of its encoding; every word the encoder does not know adds to the `<unk>` row, which ends up as
+    their average; rows no line names stay zero."""
+    unk = text_encoder.unk_idx
+    subword = text_encoder.token_type == "subword"
+    n_unk = 0
+    with open(embedding_filepath, "r") as f:
+        dim = int(f.readline().split()[1])
+        table = np.zeros((text_encoder.vocab_size, dim))
+        for line in f:
+            word, values = line.strip().split(" ", 1)
+            if word == "</s>":
+                word = "<eos>"
+            idx = text_encoder.spm.piece_to_id(word) if subword else text_encoder.encode(word)[0]
+            vec = np.asarray([float(v) for v in values.split(" ")])
+            if idx == unk:
+                n_unk += 1
+                table[idx] += vec
+            else:
+                table[idx] = vec
+    if n_unk:
+        table[unk] /= n_unk
+    return table
+
+
 def _argmax(pred):
     """hypothesis read-out: the gfx950 top-1 kernel for device tensors (host tensors only occur in
     CPU-side unit tests of this metric helper)"""

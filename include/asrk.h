@@ -454,6 +454,56 @@ int asrk_embedding_fwd_f32(const int64_t *idx, const float *W, float *out, int64
 int asrk_embedding_bwd_f32(const int64_t *idx, const float *dout, float *dW_acc, int64_t n, int D,
                            int V, void *stream);
 
+/* ---- word-embedding plug-in (src/plugin.py:7-160 EmbeddingRegularizer; csrc/emb_fuse.hip) ---------------------
+ * Rows n = 0..N-1 (N = B*L in training, the live beam rows at a decode position), vocabulary V, embedding width E.
+ * None of these kernels uses a float atomic: every sum has a fixed order, so results are bit-reproducible.
+ *
+ * Fused distribution (src/plugin.py:103-123): with a_v = max(temp_v, 0) * emb_logit[n,v], pd = softmax(dec_logit[n,:]),
+ * pe = softmax(a), s_v = sigmoid(lam_v) (lam_is_logit != 0) or lam_v,
+ *     y[n,v] = log((1 - s_v) * pd_v + s_v * pe_v + eps).
+ * dec_logit has leading dimension ld >= V; emb_logit, y and every gradient are dense [N,V].  temp and lam hold 1 or V
+ * floats (temp_len / lam_len; anything else: ASRK_EINVAL).  stats [N,4] receives the row maximum and the sum of
+ * exponentials of both softmaxes; the backward recomputes pd / pe from them.
+ * bwd: g = dL/dy [N,V] -> d_dec, d_emb [N,V]; dtemp [temp_len] / dlam [lam_len] when not NULL (summed over rows, and
+ *      over v for a scalar; dlam is with respect to the logit when lam_is_logit).  ws: asrk_emb_fuse_bwd_ws_bytes
+ *      (want_* = the matching pointer is not NULL) bytes of device scratch, 4-byte aligned; ASRK_EWORKSPACE if smaller.
+ * Both: ASRK_EINVAL for a NULL pointer, V <= 0, ld < V or a bad length, checked before any device call. */
+size_t asrk_emb_fuse_bwd_ws_bytes(int N, int V, int temp_len, int lam_len, int want_dtemp, int want_dlam);
+int asrk_emb_fuse_fwd_f32(const float *dec_logit, int ld, const float *emb_logit, const float *temp, int temp_len,
+                          const float *lam, int lam_len, int lam_is_logit, float eps, int N, int V, float *y,
+                          float *stats, void *stream);
+int asrk_emb_fuse_bwd_f32(const float *g, const float *dec_logit, int ld, const float *emb_logit, const float *temp,
+                          int temp_len, const float *lam, int lam_len, int lam_is_logit, float eps, const float *stats,
+                          int N, int V, float *d_dec, float *d_emb, float *dtemp, float *dlam, void *ws,
+                          size_t ws_bytes, void *stream);
+/* Cosine embedding loss against table[label] (src/plugin.py:137-155; nn.CosineEmbeddingLoss(reduction='none'), target
+ * +1): row_loss[n] = 1 - x.y / sqrt((|x|^2 + 1e-12)(|y|^2 + 1e-12)) with y = table[label[n]] read in place, 0 where
+ * label[n] == 0 (or outside the table); loss[0] = mean_b(sum_t row_loss[b,t] / count[b]), count[b] = #{t: label != 0}
+ * (an utterance without labels gives NaN, as in the reference).  x [B*L,E], table [table_rows,E], label [B,L].
+ * bwd: gout = dL/dloss (device scalar) -> dx [B*L,E] and, when not NULL, dy [B*L,E] = the gradient of the gathered
+ *      rows; for a trainable table asrk_cos_emb_table_grad_f32 turns it into dtable [table_rows,E] (zeroed first):
+ *      dtable[v] = sum of dy[n] over label[n] == v in row order - a fixed order, unlike the atomic scatter of
+ *      asrk_embedding_bwd_f32, so repeated labels give the same bits every run. */
+int asrk_cos_emb_loss_fwd_f32(const float *x, const float *table, int64_t table_rows, const int64_t *label, int B,
+                              int L, int E, float *row_loss, float *count, float *loss, void *stream);
+int asrk_cos_emb_loss_bwd_f32(const float *x, const float *table, int64_t table_rows, const int64_t *label, int B,
+                              int L, int E, const float *count, const float *gout, float *dx, float *dy,
+                              void *stream);
+/* NLLLoss(ignore_index) over log-probabilities (bin/train_asr.py:62): sums[0] = sum of -logp[r, t_r] over the rows
+ * with t_r != ignore_index, sums[1] = their number (mean = sums[0] / sums[1]; no such row: 0/0).
+ * bwd: dlogp[r,:] = 0 except dlogp[r, t_r] = -gscale[0] on counted rows; gscale is a device scalar. */
+int asrk_cos_emb_table_grad_f32(const float *dy, const int64_t *label, int N, int E, int64_t table_rows,
+                                float *dtable, void *stream);
+int asrk_nll_loss_fwd_f32(const float *logp, int rows, int V, int ld, const int64_t *targets, int ignore_index,
+                          float *sums, void *stream);
+int asrk_nll_loss_bwd_f32(int rows, int V, int ld, const int64_t *targets, int ignore_index, const float *gscale,
+                          float *dlogp, void *stream);
+/* Row L2 normalisation (src/plugin.py:107-108; F.normalize): y = x / max(|x|, eps), norm[r] = |x_r|.
+ * bwd: dx = (dy - y (y.dy)) / |x| where |x| >= eps, dy / eps below the clamp. */
+int asrk_l2norm_fwd_f32(const float *x, float *y, float *norm, int rows, int D, float eps, void *stream);
+int asrk_l2norm_bwd_f32(const float *y, const float *dy, const float *norm, float *dx, int rows, int D, float eps,
+                        void *stream);
+
 /* ---- the attention-decoder ("speller") loop as one call per direction ---------------------------
  * Replaces the teacher-forced decode loop of ASR.forward (src/asr.py:112-148 with tf_rate == 1) and
  * the autograd graph under it: per step Attention.forward (src/asr.py:277-313) ->
