@@ -7,6 +7,7 @@ handed to a hand-written gfx950 kernel.  Nothing here falls back to ATen math.
 import collections
 import ctypes
 
+import numpy as np
 import torch
 from torch.autograd import Function
 
@@ -1602,3 +1603,71 @@ def spec_augment(x, lens, params, n_fmask, n_tmask, fill=0.0, channels=1):
     _lib.check(_L().asrk_spec_augment_f32(_p(xc), _p(y), B, T, F, F // channels, channels, _p(lens), _p(params),
                                           int(n_fmask), int(n_tmask), float(fill), _stream()), "spec_augment")
     return y
+
+
+_RESAMPLE_TAPS = {}
+RESAMPLE_LOWPASS_WIDTH = 6
+RESAMPLE_ROLLOFF = 0.99
+
+
+def resample_width(orig, new):
+    """half-width of the polyphase filter in input samples: ceil(W * orig / (min(orig, new) * rolloff)), taken exactly
+    (the library derives the same number: include/asrk.h, asrk_resample_rows_f32)"""
+    return -(-100 * RESAMPLE_LOWPASS_WIDTH * orig // (99 * min(orig, new)))
+
+
+def resample_taps(orig, new):
+    """the tap table h [new, 2*width + orig] of one ratio in float64 (torchaudio's sinc_interp_hann kernel)"""
+    W = float(RESAMPLE_LOWPASS_WIDTH)
+    base = min(orig, new) * RESAMPLE_ROLLOFF
+    width = resample_width(orig, new)
+    j = np.arange(new, dtype=np.float64)[:, None]
+    k = np.arange(2 * width + orig, dtype=np.float64)[None, :]
+    t = np.clip((-j / new + (k - width) / orig) * base, -W, W)
+    return np.sinc(t) * np.cos(np.pi * t / (2.0 * W)) ** 2 * (base / orig)      # np.sinc(t) = sin(pi t) / (pi t)
+
+
+def _resample_taps_dev(orig, new, device):
+    key = (orig, new, str(device))
+    tab = _RESAMPLE_TAPS.get(key)
+    if tab is None:
+        tab = torch.from_numpy(np.ascontiguousarray(resample_taps(orig, new), dtype=np.float32)).to(device)
+        _RESAMPLE_TAPS[key] = tab
+    return tab
+
+
+def resample_rows(x, n_host, ratio_idx, ratios, scale=1.0):
+    """Polyphase resampling of every row of a padded waveform batch by its own ratio, in one launch
+    (csrc/resample.hip; semantics: include/asrk.h asrk_resample_rows_f32).  x [B, ld_in] int16 or float32 on the GPU;
+    n_host [B] the rows' sample counts and ratio_idx [B] their indices into `ratios`, a list of coprime (orig, new)
+    pairs, all ON THE HOST.  Row b is slowed down / sped up by speed = orig / new.  -> (y [B, ld_out] float32, already
+    multiplied by `scale`, columns beyond a row's own length left unwritten; n_out int64 numpy [B]).  The output
+    lengths are computed here on the host: nothing is read back from the device."""
+    _require_gpu(x)
+    if x.dim() != 2 or x.dtype not in (torch.int16, torch.float32) or not x.is_contiguous():
+        raise ValueError("resample_rows expects a contiguous [B, ld_in] int16 or float32 batch")
+    B, ld_in = x.shape
+    n = np.ascontiguousarray(np.asarray(n_host, dtype=np.int64).reshape(-1))
+    idx = np.ascontiguousarray(np.asarray(ratio_idx, dtype=np.int32).reshape(-1))
+    rat = np.ascontiguousarray(np.asarray(ratios, dtype=np.int32).reshape(-1, 2))
+    if n.shape[0] != B or idx.shape[0] != B:
+        raise ValueError("resample_rows: %d rows, %d lengths, %d ratio indices" % (B, n.shape[0], idx.shape[0]))
+    if B and (rat.shape[0] == 0 or idx.min() < 0 or idx.max() >= rat.shape[0] or rat.min() < 1):
+        raise ValueError("resample_rows: ratio index outside the %d ratio(s) given, or a non-positive ratio"
+                         % rat.shape[0])
+    n_out = (rat[idx, 1].astype(np.int64) * n + rat[idx, 0] - 1) // rat[idx, 0] if B else np.zeros(0, np.int64)
+    ld_out = (int(n_out.max()) + 3) // 4 * 4 if B else 0
+    y = torch.empty((B, ld_out), dtype=torch.float32, device=x.device)
+    if B == 0:
+        return y, n_out
+    tabs = [None if (o, w) == (1, 1) else _resample_taps_dev(int(o), int(w), x.device) for o, w in rat.tolist()]
+    taps = (ctypes.c_void_p * len(tabs))(*[None if t is None else t.data_ptr() for t in tabs])
+    # the kernel's copies of the lengths and indices: one pinned buffer, one non-blocking upload
+    meta = torch.empty(B + (B + 1) // 2, dtype=torch.int64).pin_memory()
+    meta[:B] = torch.from_numpy(n)
+    meta[B:].view(torch.int32)[:B] = torch.from_numpy(idx)
+    meta_dev = meta.to(x.device, non_blocking=True)
+    _lib.check(_L().asrk_resample_rows_f32(_p(x), x.element_size(), ld_in, n.ctypes.data, meta_dev.data_ptr(),
+                                           idx.ctypes.data, meta_dev.data_ptr() + 8 * B, B, rat.ctypes.data, taps,
+                                           rat.shape[0], _p(y), ld_out, float(scale), _stream()), "resample_rows")
+    return y, n_out

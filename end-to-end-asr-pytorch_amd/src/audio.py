@@ -9,6 +9,8 @@ Same module names, constructor arguments, tensor shapes between stages ([C, D, T
 import inspect
 import math
 import wave as _wave
+import zlib
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -321,11 +323,21 @@ class ExtractAudioFeature(nn.Module):
         self.device = device
 
     def forward(self, filepath):
+        ''' filepath: a path, (waveform, sample_rate), or (waveform, sample_rate, speed): channel 0 of the waveform is
+            then speed-perturbed on the device first (the kernel of the whole-batch form, B = 1) '''
+        speed = None
         if isinstance(filepath, (tuple, list)):
-            waveform, sample_rate = filepath
+            if len(filepath) == 3:
+                waveform, sample_rate, speed = filepath
+            else:
+                waveform, sample_rate = filepath
         else:
             waveform, sample_rate = load_wav(filepath)
         waveform = waveform.to(self.device)
+        if speed is not None and float(speed) != 1.0:
+            x = _f32c(waveform[0]).reshape(1, -1)
+            y, n_out = ops.resample_rows(x, [x.shape[1]], [0], [SpeedPerturb.ratio(speed)], 1.0)
+            waveform = y[:, :int(n_out[0])]
         extract = kaldi_fbank if self.mode == "fbank" else kaldi_mfcc
         y = extract(waveform, num_mel_bins=self.num_mel_bins, channel=-1,
                     sample_frequency=sample_rate, **self.kwargs)
@@ -417,14 +429,30 @@ class BatchFeatureTransform:
         win, shift = int(sample_rate * self.frame_length * 0.001), int(sample_rate * self.frame_shift * 0.001)
         return 0 if n_samples < win else 1 + (n_samples - win) // shift
 
-    def __call__(self, waves, sample_rate):
+    def __call__(self, waves, sample_rate, speeds=None):
         """waves: list of 1-D int16 numpy arrays (raw PCM; uploaded as 2-byte samples) or float32 arrays /
-        tensors in [-1, 1) -> (feat [B, Tmax, out_dim] on the device, zero padded, feat_len LongTensor [B])"""
+        tensors in [-1, 1) -> (feat [B, Tmax, out_dim] on the device, zero padded, feat_len LongTensor [B]).
+        speeds: one speed-perturbation factor per utterance (SpeedPerturb), or None.  Utterance b is resampled on the
+        device by speeds[b] before the filterbank (one more launch: ops.resample_rows) and feat_len counts the frames
+        of the PERTURBED waveform; None, or all factors 1.0, is the plain path: no extra launch, the same bits."""
         L = _L()
         dev, B = self.device, len(waves)
         is_i16 = all(isinstance(w, np.ndarray) and w.dtype == np.int16 for w in waves)
         arrs = [w if is_i16 else torch.as_tensor(w, dtype=torch.float32).reshape(-1).numpy() for w in waves]
-        ns = [int(a.shape[0]) for a in arrs]
+        ns_src = [int(a.shape[0]) for a in arrs]
+        perturb = speeds is not None and any(float(f) != 1.0 for f in speeds)
+        if perturb:
+            if len(speeds) != B:
+                raise ValueError('%d speed factors for %d utterances' % (len(speeds), B))
+            ratios, ridx = [], []
+            for f in speeds:
+                r = SpeedPerturb.ratio(f)
+                if r not in ratios:
+                    ratios.append(r)
+                ridx.append(ratios.index(r))
+            ns = [SpeedPerturb.out_samples(n, f) for n, f in zip(ns_src, speeds)]
+        else:
+            ns = ns_src
         tb = _FbankTables.get(int(sample_rate), self.frame_length, self.frame_shift, self.feat_dim, self.low_freq,
                               self.high_freq, dev)
         ms = [self.frame_count(n, sample_rate) for n in ns]
@@ -435,7 +463,7 @@ class BatchFeatureTransform:
         out = torch.empty((B, Tmax, C * D), dtype=torch.float32, device=dev)
         if total == 0:
             return out, feat_len
-        nmax = max(ns)
+        nmax = max(ns_src)
         # persistent pinned staging buffer (pinning per batch costs more than the whole front end); rows are
         # NOT cleared: the framing kernel never reads beyond an utterance's own last frame
         tdt = torch.int16 if is_i16 else torch.float32
@@ -451,29 +479,34 @@ class BatchFeatureTransform:
         host_t = st[:need].view(B, nmax)
         host = host_t.numpy()
         for b, a in enumerate(arrs):
-            host[b, :ns[b]] = a
+            host[b, :ns_src[b]] = a
         wave = host_t.to(dev, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._staging_ev[tdt] = ev
+        sbytes, scale = (2, 1.0 / 32768.0) if is_i16 else (4, 1.0)
+        if perturb:
+            # [B, nmax] PCM -> [B, ld] float32 waveforms at the perturbed speeds, already scaled
+            wave, _ = ops.resample_rows(wave, ns_src, ridx, ratios, scale)
+            nmax, sbytes, scale = wave.shape[1], 4, 1.0
         offs = np.zeros(B + 1, dtype=np.int64)
         offs[1:] = np.cumsum(ms)
         frame_off = torch.from_numpy(offs).to(dev)
         n_host = np.asarray(ns, dtype=np.int64)
         if tb.fused:
             mel = torch.empty((total, self.feat_dim), dtype=torch.float32, device=dev)
-            _lib.check(L.asrk_fbank_logmel_batch_f32(_p(wave), 2 if is_i16 else 4, nmax, n_host.ctypes.data,
+            _lib.check(L.asrk_fbank_logmel_batch_f32(_p(wave), sbytes, nmax, n_host.ctypes.data,
                                                      _p(frame_off), B, Tmax, _p(tb.window), _p(tb.tw_fft),
                                                      _p(tb.tw_unpack), _p(tb.melT), _p(tb.mel_range), self.feat_dim,
                                                      self.feat_dim, _p(mel), tb.win, tb.shift, tb.log2n,
-                                                     1.0 / 32768.0 if is_i16 else 1.0, self.preemph,
+                                                     scale, self.preemph,
                                                      int(self.remove_dc), FLT_EPS, _stream()), 'fbank_logmel_batch')
         else:
             frames = torch.empty((total, tb.ldf), dtype=torch.float32, device=dev)
-            _lib.check(L.asrk_fbank_frames_batch_f32(_p(wave), 2 if is_i16 else 4, nmax,
+            _lib.check(L.asrk_fbank_frames_batch_f32(_p(wave), sbytes, nmax,
                                                      n_host.ctypes.data, _p(frame_off), B, Tmax, _p(tb.window),
                                                      _p(frames), tb.win, tb.shift, tb.ldf,
-                                                     1.0 / 32768.0 if is_i16 else 1.0, self.preemph,
+                                                     scale, self.preemph,
                                                      int(self.remove_dc), _stream()), 'fbank_frames_batch')
             mel = _frames_to_logmel(frames, tb, self.feat_dim)
         if self.feat_type == "mfcc":
@@ -616,6 +649,86 @@ class SpecAugment:
         return 'SpecAugment| time warp W = {} | {} freq. mask(s) <= {} of {} bins | {} time mask(s) <= min({}, {} * len) ' \
                '| fill = {}'.format(self.time_warp, self.n_freq_mask, self.freq_mask_width, self.feat_dim,
                                     self.n_time_mask, self.time_mask_width, self.time_mask_ratio, self.mask_value)
+
+
+class SpeedPerturb:
+    """Speed perturbation (the Kaldi / LibriSpeech recipe: every training utterance resampled by a factor drawn from
+    {0.9, 1.0, 1.1}; pitch and duration change together) for a padded PCM batch that is already in HBM.  A factor f is
+    the rational speed orig / new with two decimals in [0.5, 2.0] (both terms at most 100 once reduced: 1.01 = 101:100
+    is refused); the utterance is read as sampled at f * sr and converted to sr by
+    the polyphase kernel behind ops.resample_rows (csrc/resample.hip, semantics in include/asrk.h), so n samples become
+    ceil(n * new / orig).
+
+    The draw is stateless and the same on every data-parallel rank: a pure function of (seed, epoch_key, utterance
+    name), so all ranks deal a global batch by the same perturbed lengths.  `begin_epoch(key)` sets epoch_key (the
+    solver passes the step at which the epoch starts: a run resumed in mid-epoch draws the rest of that epoch from the
+    step it resumed at - a known limit)."""
+
+    KEYS = ('factors',)
+    MAX_FACTORS = 8             # RS_MAX_RATIOS of csrc/resample.hip
+    DEFAULT_FACTORS = (0.9, 1.0, 1.1)
+
+    def __init__(self, factors=DEFAULT_FACTORS, seed=0):
+        if isinstance(factors, (str, bytes)) or not isinstance(factors, (list, tuple)):
+            raise ValueError('speed_perturb: factors must be a list of numbers, got %r' % (factors,))
+        if not 1 <= len(factors) <= self.MAX_FACTORS:
+            raise ValueError('speed_perturb: between 1 and %d factors, got %d' % (self.MAX_FACTORS, len(factors)))
+        self.ratios = [self.ratio(f) for f in factors]          # validates every factor
+        self.factors = [float(f) for f in factors]
+        self.seed, self.epoch_key = int(seed), 0
+
+    @staticmethod
+    def ratio(f):
+        """factor -> the coprime (orig, new) of speed = orig / new"""
+        if isinstance(f, bool) or not isinstance(f, (int, float)) or not math.isfinite(f):
+            raise ValueError('speed_perturb: a factor must be a number, got %r' % (f,))
+        c = round(f * 100.0)
+        if abs(f * 100.0 - c) > 1e-6:
+            raise ValueError('speed_perturb: factors have at most two decimals, got %r' % (f,))
+        if not 50 <= c <= 200:
+            raise ValueError('speed_perturb: factors lie in [0.5, 2.0], got %r' % (f,))
+        q = Fraction(int(c), 100)
+        if q.numerator > 100:
+            raise ValueError('speed_perturb: %r is %d:%d in lowest terms; the resampler takes terms up to 100'
+                             % (f, q.numerator, q.denominator))
+        return q.numerator, q.denominator
+
+    @classmethod
+    def out_samples(cls, n, f):
+        """sample count of an n-sample utterance after perturbation by factor f: ceil(n * new / orig)"""
+        orig, new = cls.ratio(f)
+        return (new * int(n) + orig - 1) // orig
+
+    @classmethod
+    def from_config(cls, cfg, seed=0):
+        """cfg: the whole yaml config (a mapping); its top-level `speed_perturb:` block holds `enable` and `factors`.
+        -> None when the block is absent or `enable: false`."""
+        block = cfg.get('speed_perturb') if cfg is not None else None
+        if block is None:
+            return None
+        if not isinstance(block, dict):
+            raise ValueError('speed_perturb: expected a mapping, got %r' % (block,))
+        block = dict(block)
+        enable = block.pop('enable', True)
+        if not isinstance(enable, bool):
+            raise ValueError('speed_perturb: enable must be true or false, got %r' % (enable,))
+        unknown = sorted(set(block) - set(cls.KEYS))
+        if unknown:
+            raise ValueError('speed_perturb: unknown key(s) %s (known: enable, %s)' % (unknown, ', '.join(cls.KEYS)))
+        policy = cls(seed=seed, **block)                        # a disabled block is still checked
+        return policy if enable else None
+
+    def begin_epoch(self, epoch_key):
+        self.epoch_key = int(epoch_key)
+
+    def factor(self, name):
+        """the factor of utterance `name` in the current epoch"""
+        z = (self.seed & _M64) ^ _splitmix64(self.epoch_key & _M64) ^ zlib.crc32(name.encode())
+        return self.factors[_splitmix64(z) % len(self.factors)]
+
+    def create_msg(self):
+        return 'SpeedPerturb| factors = {} (orig:new = {}) | drawn per utterance and epoch, the same on every rank' \
+            .format(self.factors, ', '.join('%d:%d' % r for r in self.ratios))
 
 
 def create_transform(audio_config, device='cuda'):

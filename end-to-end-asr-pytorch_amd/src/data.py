@@ -78,45 +78,71 @@ class SharedShuffleSampler(Sampler):
         return self.n_draws
 
 
-def collect_audio_batch(batch, audio_transform, mode, n_jobs=1, shard=None):
+def _utt_name(path):
+    return path.split('/')[-1].split('.')[0]
+
+
+class _Speeds:
+    ''' what the collate function asks of a SpeedPerturb policy (src/audio.py), or of none: the factor of a file, its
+        sample count after perturbation, and the per-file chain's input for it '''
+
+    def __init__(self, policy):
+        self.policy = policy
+
+    def factor(self, path):
+        return self.policy.factor(_utt_name(path))
+
+    def samples(self, n, path):
+        return n if self.policy is None else self.policy.out_samples(n, self.factor(path))
+
+    def wav(self, path):
+        ''' load_wav's (waveform, sample_rate), with the file's factor appended under a policy (ExtractAudioFeature
+            then resamples on the device: the per-file chain never drops the augmentation) '''
+        return load_wav(path) if self.policy is None else load_wav(path) + (self.factor(path),)
+
+
+def collect_audio_batch(batch, audio_transform, mode, n_jobs=1, shard=None, speed_perturb=None):
     ''' [(audio_path, [token ids]), ...] (or one bucket of them) ->
         (names, feat [B,T,D] on the transform's device, feat_len [B], text [B,L])
         (reference: src/data.py:14-46).  shard = (rank, world): `batch` is the GLOBAL batch of a data-parallel step;
-        the halving rule is applied to it as a whole, then this rank keeps its length-balanced share (§8e cond. 5). '''
+        the halving rule is applied to it as a whole, then this rank keeps its length-balanced share (§8e cond. 5).
+        speed_perturb: a SpeedPerturb policy (src/audio.py) or None; under a policy every length that decides something
+        here - halving, dealing, the order within the batch, feat_len - is the PERTURBED one. '''
     if type(batch[0]) is not tuple:
         batch = batch[0]
     paths = [str(b[0]) for b in batch]
     pool = _pool(n_jobs)
     bt = getattr(audio_transform, 'batch', None)
+    sp = _Speeds(speed_perturb)
     if bt is not None and os.environ.get('ASRK_BATCH_FBANK', '1') != '0':
         try:
-            return _collect_audio_batch_device(batch, paths, bt, mode, pool, shard)
+            return _collect_audio_batch_device(batch, paths, bt, mode, pool, shard, sp)
         except _BatchPathUnsupported:
             pass
     with torch.no_grad():
         # the first utterance of a bucket is the longest transcript: its frame count decides halving
-        first = audio_transform(paths[0])
+        first = audio_transform(paths[0] if speed_perturb is None else sp.wav(paths[0]))
         if first.shape[0] > HALF_BATCHSIZE_AUDIO_LEN and mode == 'train':
             batch, paths = batch[:_half(len(batch), shard)], paths[:_half(len(batch), shard)]
         if shard is not None and shard[1] > 1:
             fc = None
             if bt is not None:                    # frame counts from the file headers: only this rank's share is extracted
                 try:
-                    fc = [first.shape[0]] + [bt.frame_count(*_num_samples_or_defer(p)) for p in paths[1:]]
+                    fc = [first.shape[0]] + [_frame_count(bt, sp, p) for p in paths[1:]]
                 except _BatchPathUnsupported:     # a header the reader rejects: extract everything to learn the lengths
                     fc = None
             if fc is not None:
                 mine = deal_global_batch(fc, *shard)
-                feats = [first if i == 0 else audio_transform(load_wav(paths[i])) for i in mine]
+                feats = [first if i == 0 else audio_transform(sp.wav(paths[i])) for i in mine]
             else:
-                allf = [first] + [audio_transform(load_wav(p)) for p in paths[1:]]
+                allf = [first] + [audio_transform(sp.wav(p)) for p in paths[1:]]
                 mine = deal_global_batch([f.shape[0] for f in allf], *shard)
                 feats = [allf[i] for i in mine]
             batch, paths = [batch[i] for i in mine], [paths[i] for i in mine]
         else:
-            waves = list(pool.map(load_wav, paths[1:])) if pool is not None else [load_wav(p) for p in paths[1:]]
+            waves = list(pool.map(sp.wav, paths[1:])) if pool is not None else [sp.wav(p) for p in paths[1:]]
             feats = [first] + [audio_transform(w) for w in waves]
-    names = [p.split('/')[-1].split('.')[0] for p in paths]
+    names = [_utt_name(p) for p in paths]
     text = [torch.LongTensor(b[1]) for b in batch]
     # descending audio length within the batch; sorted() is stable, so ties keep their order
     order = sorted(range(len(feats)), key=lambda i: feats[i].shape[0], reverse=True)
@@ -138,6 +164,12 @@ def _num_samples_or_defer(path):
         raise _BatchPathUnsupported(str(e))
 
 
+def _frame_count(bt, sp, path):
+    ''' frame count of a file from its header alone, after speed perturbation when a policy is set '''
+    n, sr = _num_samples_or_defer(path)
+    return bt.frame_count(sp.samples(n, path), sr)
+
+
 def _load_pcm_or_defer(path):
     try:
         return load_pcm(path)
@@ -145,30 +177,34 @@ def _load_pcm_or_defer(path):
         raise _BatchPathUnsupported(str(e))
 
 
-def _collect_audio_batch_device(batch, paths, bt, mode, pool, shard=None):
+def _collect_audio_batch_device(batch, paths, bt, mode, pool, shard=None, sp=_Speeds(None)):
     ''' the same contract through the whole-batch front end (src/audio.py:BatchFeatureTransform): host threads
         read raw 16-bit PCM, ONE padded int16 upload, 7 launches for the batch.  Frame counts follow from the
         sample counts (snip-edges framing), so the halving rule (src/data.py:22-24) and the descending-length
-        order (src/data.py:36-37) are decided before anything is extracted - no file is processed twice. '''
+        order (src/data.py:36-37) are decided before anything is extracted - no file is processed twice.  Under a
+        speed-perturbation policy (sp) the sample counts are the perturbed ones and the resampling is one more launch. '''
     n0, sr = _num_samples_or_defer(paths[0])
-    if bt.frame_count(n0, sr) > HALF_BATCHSIZE_AUDIO_LEN and mode == 'train':
+    if bt.frame_count(sp.samples(n0, paths[0]), sr) > HALF_BATCHSIZE_AUDIO_LEN and mode == 'train':
         batch, paths = batch[:_half(len(batch), shard)], paths[:_half(len(batch), shard)]
     if shard is not None and shard[1] > 1:
         # data parallel: the halved GLOBAL batch is dealt by length (read from the file headers); only this
         # rank's share is decoded, uploaded and extracted
-        fc = [bt.frame_count(*_num_samples_or_defer(p)) for p in paths]
+        fc = [_frame_count(bt, sp, p) for p in paths]
         mine = deal_global_batch(fc, *shard)
         batch, paths = [batch[i] for i in mine], [paths[i] for i in mine]
     loaded = list(pool.map(_load_pcm_or_defer, paths)) if pool is not None else [_load_pcm_or_defer(p) for p in paths]
     if any(r[1] != sr for r in loaded):
         raise _BatchPathUnsupported('mixed sample rates in one batch')
     pcm = [r[0] for r in loaded]
-    frames = [bt.frame_count(len(x), sr) for x in pcm]
+    frames = [bt.frame_count(sp.samples(len(x), p), sr) for x, p in zip(pcm, paths)]
     # descending audio length within the batch; sorted() is stable, so ties keep their order
     order = sorted(range(len(pcm)), key=lambda i: frames[i], reverse=True)
     with torch.no_grad():
-        audio_feat, audio_len = bt([pcm[i] for i in order], sr)
-    names = tuple(paths[i].split('/')[-1].split('.')[0] for i in order)
+        if sp.policy is None:
+            audio_feat, audio_len = bt([pcm[i] for i in order], sr)
+        else:
+            audio_feat, audio_len = bt([pcm[i] for i in order], sr, speeds=[sp.factor(paths[i]) for i in order])
+    names = tuple(_utt_name(paths[i]) for i in order)
     text = pad_sequence([torch.LongTensor(batch[i][1]) for i in order], batch_first=True)
     return names, audio_feat, audio_len, text
 
@@ -253,9 +289,11 @@ def load_textset(n_jobs, use_gpu, pin_memory, corpus, text):
     return tr_set, dv_set, tokenizer.vocab_size, tokenizer, data_msg
 
 
-def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text):
+def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, speed_perturb=None):
     ''' (reference: src/data.py:128-157) -> (tr_loader, dv_loader, feat_dim, vocab_size, tokenizer, msg).
-        `use_gpu` must be true (there is no CPU feature path); `pin_memory` is accepted and unused. '''
+        `use_gpu` must be true (there is no CPU feature path); `pin_memory` is accepted and unused.
+        speed_perturb: a SpeedPerturb policy (src/audio.py) for the TRAINING loader's collate function, or None; the
+        dev / test loaders never perturb. '''
     if not use_gpu:
         raise RuntimeError("the feature pipeline runs in gfx950 kernels; --cpu is not supported")
     audio_transform, feat_dim = create_transform(audio.copy(), device='cuda')
@@ -271,7 +309,8 @@ def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text):
         # one process per GPU: every rank draws the same GLOBAL batches (batch_size stays PER RANK: weak scaling of
         # the global batch) and keeps its length-balanced share of each (deal_global_batch)
         sampler, shard = _dp_sampler(len(tr_set), tr_loader_bs, world, shuffle), (rank, world)
-    collect_tr = partial(collect_audio_batch, audio_transform=audio_transform, mode=mode, n_jobs=n_jobs, shard=shard)
+    collect_tr = partial(collect_audio_batch, audio_transform=audio_transform, mode=mode, n_jobs=n_jobs, shard=shard,
+                         speed_perturb=speed_perturb if mode == 'train' else None)
     collect_dv = partial(collect_audio_batch, audio_transform=audio_transform, mode='test', n_jobs=n_jobs)
     tr_set = DataLoader(tr_set, batch_size=tr_loader_bs, shuffle=shuffle and sampler is None,
                         sampler=sampler, drop_last=shuffle,

@@ -892,6 +892,33 @@ int asrk_fbank_logmel_batch_f32(const void *wave, int sample_bytes, int64_t ld_w
 int asrk_spec_augment_f32(const float *x, float *y, int B, int T, int ld, int D, int C, const int64_t *lens,
                           const int32_t *params, int n_fmask, int n_tmask, float fill, void *stream);
 
+/* ---- Speed perturbation on the padded PCM batch (training input augmentation; sits between the PCM upload and
+ * asrk_fbank_*_batch_f32, which then take y with sample_bytes = 4, scale = 1) ------------------------------------------
+ * x [B, ld_in] of int16 (sample_bytes 2) or f32 (sample_bytes 4), `scale` as in asrk_fbank_frames_batch_f32; row b
+ * holds n[b] samples.  y [B, ld_out] f32 (x != y).  ratios_host [n_ratios][2] int32 (HOST) = (orig, new), coprime
+ * positive integers; row b uses ratio ratio_idx[b].  Speed = orig / new: the row is taken as sampled at orig/new times
+ * the rate and converted to the rate (torchaudio's sinc_interp_hann resampler, lowpass_filter_width W = 6, rolloff 0.99):
+ *     base = min(orig, new) * 0.99, width = ceil(W * orig / base) taken exactly = ceil(100 W orig / (99 min(orig, new))),
+ *     taps = 2*width + orig;  table h [new][taps] f32 (device; the caller builds it in float64 and rounds once):
+ *     t = clamp((-j/new + (k - width)/orig) * base, -W, W),  h[j][k] = sinc(pi t) * cos^2(pi t / (2W)) * base/orig;
+ *     n_out = (new*n + orig - 1) / orig  (integers);  for o = i*new + j < n_out:
+ *     y[o] = sum_k h[j][k] * (x[i*orig + k - width] * scale),  x = 0 outside 0..n-1,
+ *     accumulated in f32 with fused multiply-adds in ascending k, starting from 0.
+ * Ratio (1, 1) is not filtered: y[o] = x[o] * scale bit for bit (its table pointer is not read and may be NULL).
+ * taps_host [n_ratios] (HOST) holds the DEVICE pointers of the tables.  Columns o >= n_out[b] of y are not written.
+ * n and ratio_idx are passed twice: the HOST arrays are checked and size the launch; the DEVICE copies are what the
+ * kernel reads (clamped there to the buffers: a copy that disagrees cannot make it leave x or y).  One launch, no atomics;
+ * 16-byte stores when y is 16-byte aligned and ld_out is a multiple of 4, element stores otherwise.
+ * Limits: orig, new <= 100 and 1/2 <= orig/new <= 2 (speeds with two decimals in [0.5, 2.0]); n_ratios <= 8.
+ * ASRK_ESHAPE, all checked before any device call: a negative size, sample_bytes not 2 or 4, x == y, n_ratios > 8, a
+ * ratio outside the limits or not coprime, n[b] outside 0..ld_in, ratio_idx[b] outside 0..n_ratios-1, ld_out < n_out[b],
+ * a NULL pointer with work to do (any host array with B > 0; x, y, a device copy or a used table with an output sample
+ * to compute).  B == 0, or no output sample at all, returns 0 without a launch. */
+int asrk_resample_rows_f32(const void *x, int sample_bytes, int64_t ld_in, const int64_t *n_host, const int64_t *n_dev,
+                           const int32_t *ratio_idx_host, const int32_t *ratio_idx_dev, int B,
+                           const int32_t *ratios_host, const float *const *taps_host, int n_ratios, float *y,
+                           int64_t ld_out, float scale, void *stream);
+
 /* ---- CTC loss (bin/train_asr.py:49,123-124 -> torch.nn.CTCLoss(blank=0)) ---------------
  * log_probs element (t,b,c) at lp[t*stride_t + b*stride_b + c]; targets [B,L] int64 (row stride
  * tgt_stride) zero-padded; input_lengths/target_lengths int64 [B].

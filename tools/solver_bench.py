@@ -6,7 +6,7 @@ half-batch rule of src/data.py:22-24 cuts every batch whose first utterance is l
 what bench.py measures on a resident batch can be compared with what a user of main.py gets: file reads, the whole-batch
 fbank front end, collation, loss assembly, clipping, the update, logging cadence, everything.
 
-    python tools/solver_bench.py [--steps 20] [--warmup 6] [--workload cfg3|cfg2] [--specaug]
+    python tools/solver_bench.py [--steps 20] [--warmup 6] [--workload cfg3|cfg2] [--specaug] [--speed]
 
 Prints one JSON line: ms/step of Solver.exec, ms/step of bench.py's step on a resident batch of the same shapes in the
 same process, and the host-side syncs the loop performed."""
@@ -65,6 +65,8 @@ def main():
     ap.add_argument("--utterances", type=int, default=3200)
     # the same loop with the default SpecAugment policy (top-level `specaug:` block) between fetch_data and the model
     ap.add_argument("--specaug", action="store_true")
+    # the same loop with the default speed perturbation (top-level `speed_perturb:` block) in the training collate
+    ap.add_argument("--speed", action="store_true")
     args = ap.parse_args()
     bench = importlib.import_module("bench")
     w = bench.WORKLOADS[args.workload]
@@ -82,6 +84,8 @@ def main():
     }
     if args.specaug:
         cfg["specaug"] = {"enable": True}
+    if args.speed:
+        cfg["speed_perturb"] = {"enable": True}
     cfg_path = os.path.join(tmp, "cfg.yaml")
     yaml.safe_dump(cfg, open(cfg_path, "w"))
     main_mod = importlib.import_module(PKG + ".main")
@@ -143,7 +147,7 @@ def main():
     print(json.dumps({
         "what": "Solver.exec of bin/train_asr.py on a synthetic LibriSpeech-layout corpus (wav read + whole-batch fbank "
                 "front end + collate + model + losses + clip + Adadelta) vs bench.py's step on a resident batch",
-        "workload": args.workload, "specaug": bool(args.specaug), "batch_feat_shape": feat_shape, "batch_txt_shape": txt_shape,
+        "workload": args.workload, "specaug": bool(args.specaug), "speed_perturb": bool(args.speed), "batch_feat_shape": feat_shape, "batch_txt_shape": txt_shape,
         "steps": args.steps, "warmup": args.warmup,
         "solver_ms_per_step": dt * 1e3, "solver_frames_per_s": frames / dt,
         "bench_step_ms_per_step": dt_bench * 1e3, "bench_frames_per_s": w["B"] * w["T"] / dt_bench,
