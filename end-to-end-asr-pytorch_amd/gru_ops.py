@@ -164,12 +164,7 @@ class GRURecLayerFn(Function):
         Y = torch.empty((M, ldy), dtype=torch.float32, device=dev)
         wsp = _ops.lstm_workspace(dev)
         xc_ = _ops._Exchange(L, T, B, H, ndir, 0, dev)
-        mode = {None: 0, 'concat': 1, 'drop': 2}[pyr_style if pyr_rate > 1 else None]
-        Y2 = None
-        if mode == 1:
-            Y2 = torch.empty((T // pyr_rate, B, pyr_rate * ldy), dtype=torch.float32, device=dev)
-        elif mode == 2:
-            Y2 = torch.empty(((T + pyr_rate - 1) // pyr_rate, B, ldy), dtype=torch.float32, device=dev)
+        mode, Y2 = _ops._pyramid_out(T, B, ldy, pyr_rate, pyr_style, dev)
         _lib.check(L.asrk_gru_rec_fwd_f32(_p(G), _p(ws[0][1]), _p(ws[1][1] if ndir == 2 else None), _p(Y), T, B,
                                           H, ndir, _p(xc_.buf), xc_.prefilled, _p(wsp), _p(Y2), mode,
                                           max(1, pyr_rate), xc_.flags, _stream()), "gru_rec_fwd")
@@ -197,18 +192,12 @@ class GRURecLayerFn(Function):
         mode, rate = ctx.pyr
         dYc = _f32c(dY)
         wsp = _ops.lstm_workspace(dev)
-        _ops._note_bptt_plan(L, T, B, H, ndir)
-        xc_ = _ops._Exchange(L, T, B, H, ndir, 1, dev)
+        with _ops._bptt_launch(L, T, B, H, ndir, ctx.has_bias, G, dev) as (xc_, db_all):
+            db = db_all if _ops._db_in_kernel(ctx.has_bias, B) else None
+            _lib.check(L.asrk_gru_rec_bwd_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(Y), _p(dYc), T, B, H, ndir,
+                                              _p(xc_.buf), xc_.prefilled, _p(wsp), _p(db), mode, rate, xc_.flags,
+                                              _stream()), "gru_rec_bwd")
         f32 = dict(dtype=torch.float32, device=dev)
-        db_all = torch.empty((ndir, 4 * H), **f32) if ctx.has_bias else None
-        db_in_kernel = ctx.has_bias and B <= 32          # <= 2 batch groups: order-independent atomics (ops.py)
-        _lib.check(L.asrk_gru_rec_bwd_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(Y), _p(dYc), T, B, H, ndir,
-                                          _p(xc_.buf), xc_.prefilled, _p(wsp), _p(db_all if db_in_kernel else None),
-                                          mode, rate, xc_.flags, _stream()), "gru_rec_bwd")
-        xc_.done()
-        if ctx.has_bias and not db_in_kernel:
-            _ops.colsum(G, M, ndir * 4 * H, ndir * 4 * H, db_all)
-        _ops._gemm_phase_begins()
         dG = G
         ws = [w_ih_f] + ([w_ih_r] if ndir == 2 else [])
         dx = None

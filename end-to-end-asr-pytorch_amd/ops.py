@@ -5,6 +5,7 @@ bookkeeping only; every tensor that reaches this module is turned into a raw dev
 handed to a hand-written gfx950 kernel.  Nothing here falls back to ATen math.
 """
 import collections
+import contextlib
 import ctypes
 
 import numpy as np
@@ -433,7 +434,8 @@ _REC_PANELS = _os.environ.get("ASRK_REC_PANELS", "1") != "0"
 _REC_SKIP_DG = True
 # free[(device, stream, rows, K)] = [[buffer, 0, last_use_tick], ...]; "seen" = shapes asked for before
 _panel_pool = {"free": {}, "bytes": 0, "tick": 0, "seen": {}, "stats": {"hit": 0, "miss": 0, "skipped": 0, "evicted": 0}}
-_panel_state = {"hint": False, "handover": None, "stats": {"emitted": 0, "consumed": 0, "dg": 0}}
+_panel_state = {"hint": False, "handover": None,
+                "stats": {"emitted": 0, "consumed": 0, "dg": 0, "dgt": 0, "no_dg": 0, "dw_ih_splitk": 0}}
 
 
 class _BlankPanel:
@@ -809,6 +811,118 @@ def pyramid(x_tm, rate, style):
 
 
 # --------------------------------------------------------------------------- LSTM layer
+def _pyramid_out(T, B, F, rate, style, dev, zero=False):
+    """-> (mode, Y2): the recurrence kernels' time-reduction mode (0 none, 1 'concat', 2 'drop'; src/module.py:141-153)
+    and the reduced output [T', B, F'] they store beside the layer output [T, B, F] (None for mode 0)"""
+    mode = {None: 0, 'concat': 1, 'drop': 2}[style if rate > 1 else None]
+    if mode == 0:
+        return 0, None
+    shape = (T // rate, B, rate * F) if mode == 1 else ((T + rate - 1) // rate, B, F)
+    return mode, zeros(shape, dev) if zero else torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _db_in_kernel(has_bias, B):
+    # The bias gradient (column sums of dG) comes out of the BPTT kernel itself.  In-kernel accumulation adds one partial
+    # sum per BATCH GROUP (16 or 32 rows) to each element with a float atomic: with <= 2 groups (B <= 32, every BASELINE
+    # workload) the result does not depend on the arrival order (a + b == b + a, the first add lands on an exact 0), i.e.
+    # it is bit-reproducible; with more groups the order would matter, so those shapes take the deterministic column-sum
+    # pass.
+    return has_bias and B <= 32
+
+
+@contextlib.contextmanager
+def _bptt_launch(L, T, B, H, ndir, has_bias, G, dev):
+    """What surrounds the persistent BPTT launch of an LSTM or GRU layer (G [T*B, ndir*4H]: gates in, dG out):
+        with _bptt_launch(...) as (x, db_all):  enqueue the kernel with the exchange x, bias sums to db_all if _db_in_kernel
+    On exit the exchange goes back to its pool, the bias sums the kernel did not take are column sums of dG, and the
+    layer's GEMM phase begins."""
+    _note_bptt_plan(L, T, B, H, ndir)
+    x = _Exchange(L, T, B, H, ndir, 1, dev)
+    db_all = torch.empty((ndir, 4 * H), dtype=torch.float32, device=dev) if has_bias else None
+    yield x, db_all
+    x.done()
+    if has_bias and not _db_in_kernel(has_bias, B):
+        colsum(G, T * B, ndir * 4 * H, ndir * 4 * H, db_all)
+    _gemm_phase_begins()
+
+
+# What one LSTM layer backward launches is decided by lstm_bwd_plan and executed by LSTMLayerFn.backward.  The schedules
+# of the weight-gradient GEMMs:
+STREAM = "STREAM"                                 # both directions on the main stream
+SIDE_ALL = "SIDE_ALL"                             # both directions on the side stream, as background work
+SIDE_REVERSE_SHARED = "SIDE_REVERSE_SHARED"       # reverse on the side stream; both read the ONE dG^T panel
+SIDE_REVERSE = "SIDE_REVERSE"                     # reverse on the side stream, f32 GEMMs
+IH_PANELS, IH_SPLITK, IH_F32 = "panels", "panels_splitk", "f32"      # dW_ih: each stacked (rows_ih = 8H) or per direction
+# defer_release: the pooled dG^T panel goes back at the end of the backward pass whatever else is pending (otherwise right
+# after the launches, unless side-stream work of this pass is pending then)
+LstmBwdPlan = collections.namedtuple("LstmBwdPlan", "pG pGT db_in_kernel skip_dg rows_ih dw_ih_route dw_hh_panels "
+                                                    "schedule defer_release")
+
+
+def lstm_bwd_plan(T, B, Din, H, ndir, has_bias, needs_dx, stacked, can_defer, to_scratch, beside_bptt, bf_bwd, share_env,
+                  skip_dg_switch, takes_split, take_panel):
+    """Pure: no tensor, stream, device or environment variable is touched.  stacked: the forward kept a w_stack;
+    to_scratch: no gradient destination is registered for w_ih; beside_bptt: _defer_beside_bptt() after _note_bptt_plan;
+    bf_bwd: _REC_PANELS and a bf16x6 BPTT plan; share_env: ASRK_SHARE_PANELS != "0"; skip_dg_switch: _REC_SKIP_DG;
+    takes_split(M, N, K): the split GEMM's routing rule; take_panel(rows, K) -> a pooled panel or None."""
+    M = T * B
+    # the input-gradient GEMM dX = dG [W_ih_f; W_ih_r] multiplies dG as its row-major A panel, the weight-gradient GEMMs
+    # multiply dG^T as theirs: the BPTT kernel writes both itself where its plan can (bf16x6) and the GEMMs run in
+    # stream order (the wide layers; side-stream consumers would outlive the pooled buffer)
+    pG = pGT = None
+    if bf_bwd and needs_dx and stacked and takes_split(M, Din, 8 * H):
+        pG = take_panel(M, 8 * H)
+    # Weight gradients contract over the tokens with dG^T as the left operand three times (dW_ih, dW_hh of both
+    # directions): on the split-GEMM path dG^T (and Y^T, X^T) are split ONCE into bf16 panels and the GEMMs take row / k
+    # ranges of them.  Needs every direction's GEMMs to see the one set of panels (not SIDE_REVERSE).
+    share0 = share_env and T > 1 and H % 128 == 0 and B % 8 == 0 and takes_split(4 * H, H, (T - 1) * B)
+    if bf_bwd and share0 and B % 16 == 0 and not beside_bptt:
+        pGT = take_panel(ndir * 4 * H, M)
+    # both directions' dW_ih share one launch only when they are computed on the same stream - and only into scratch:
+    # with a data-parallel engine each direction's GEMM writes its rows straight into that weight's slice of the
+    # gradient bucket (two launches of 4H rows: still >= 2 full rounds of tiles on the wide layers)
+    rows_ih = 8 * H if stacked and (needs_dx or not can_defer) and to_scratch else 4 * H
+    wide_ih = Din % 4 == 0 and takes_split(rows_ih, Din, M)
+    # A NARROW input (cfg3's bottom layer: Din = 80) leaves dW_ih = dG^T X too few output tiles for the split GEMM's
+    # routing rule, yet its K is as deep as the wide layers': it multiplies the dG^T panel too, K cut into slices that a
+    # second kernel sums in a fixed order, one launch over both directions' rows where the result goes to scratch.
+    # (Until round 6 it ran as exact-f32 GEMMs that read the f32 dG again: 3.4 ms of kernels per cfg3 step.)
+    narrow_ih = pGT is not None and Din % 4 == 0 and not wide_ih
+    if narrow_ih and stacked and to_scratch:
+        rows_ih = 8 * H
+    # Does anything read the f32 dG?  Not when every weight gradient multiplies dG^T (with pGT no schedule is
+    # SIDE_REVERSE; dW_ih takes panels when Din % 4 == 0), dX is not wanted or multiplies the dG panel, and the bias
+    # gradient was summed in the kernel: then the kernel keeps its four 4-byte stores per cell and step.
+    db_in_kernel = _db_in_kernel(has_bias, B)
+    skip_dg = bool(skip_dg_switch and pGT is not None and Din % 4 == 0 and (not needs_dx or pG is not None)
+                   and (db_in_kernel or not has_bias))
+    if not (can_defer and (beside_bptt or not needs_dx)):
+        # a BPTT kernel that owns every CU follows (_defer_beside_bptt: a GEMM beside it is PARKED), or the gradients'
+        # consumer is no plain AccumulateGrad
+        schedule = STREAM
+    elif needs_dx or ndir == 1:
+        schedule = SIDE_ALL        # off the critical path: the next layer's BPTT does not need dW / db
+    elif pGT is None:
+        # bottom layer (no input gradient wanted): no BPTT follows, nothing to hide behind.  Its small GEMMs (dW_ih with
+        # Din = 80, column sums) leave CUs idle one at a time, so the two directions run side by side: reverse on the
+        # side stream, forward on the main stream.
+        schedule = SIDE_REVERSE
+    elif Din % 4 == 0:
+        # bottom layer with the dG^T panel from the kernel: every weight gradient multiplies panels (dW_ih with a wide
+        # input like the layers above, with a narrow one through the split-K launch) and fills the chip on its own.
+        # (Until round 6 the narrow-input case ran its directions on two streams beside each other for the sake of the
+        # small f32 dW_ih GEMMs; the 256-tile dW_hh launches only serialised there.)
+        schedule = STREAM
+    else:
+        # the same with an input width no panel takes: dW_hh multiplies row ranges of the ONE dG^T panel (and of Y^T,
+        # split before the streams fork), dW_ih reads the f32 dG; the directions run side by side, the pooled panel
+        # goes back at the end of the backward pass (after the streams re-join)
+        schedule = SIDE_REVERSE_SHARED
+    panels = bool(share0) and schedule != SIDE_REVERSE
+    route = IH_SPLITK if narrow_ih else IH_PANELS if panels and wide_ih else IH_F32
+    return LstmBwdPlan(pG, pGT, db_in_kernel, skip_dg, rows_ih, route, panels, schedule, schedule == SIDE_REVERSE_SHARED)
+
+
 class LSTMLayerFn(Function):
     """One (bi)directional LSTM layer on a time-major sequence [T,B,Din] -> [T,B,ndir*H].
 
@@ -880,12 +994,7 @@ class LSTMLayerFn(Function):
         C = torch.empty((M, ndir * H), dtype=torch.float32, device=dev)
         ws = lstm_workspace(dev)
         xc_ = _Exchange(L, T, B, H, ndir, 0, dev)
-        mode = {None: 0, 'concat': 1, 'drop': 2}[pyr_style if pyr_rate > 1 else None]
-        Y2 = None
-        if mode == 1:
-            Y2 = torch.empty((T // pyr_rate, B, pyr_rate * ndir * H), dtype=torch.float32, device=dev)
-        elif mode == 2:
-            Y2 = torch.empty(((T + pyr_rate - 1) // pyr_rate, B, ndir * H), dtype=torch.float32, device=dev)
+        mode, Y2 = _pyramid_out(T, B, ndir * H, pyr_rate, pyr_style, dev)
         rate = max(1, pyr_rate)
         out_panel = None
         if (_REC_PANELS and _panel_state["hint"] and mode in (0, 1) and (mode == 0 or T // rate > 0) and
@@ -930,72 +1039,39 @@ class LSTMLayerFn(Function):
         mode, rate = ctx.pyr
         dYc = _f32c(dY)        # plain: [T,B,ldy]; fused time reduction: the reduced layout, read in place
         ws = lstm_workspace(dev)
-        # G (activated gates) -> dG (pre-activation gradients), in place
-        _note_bptt_plan(L, T, B, H, ndir)
-        xc_ = _Exchange(L, T, B, H, ndir, 1, dev)
-        # the bias gradient (column sums of dG) comes out of the BPTT kernel itself
-        db_all = torch.empty((ndir, 4 * H), dtype=torch.float32, device=dev) if ctx.has_bias else None
-        # In-kernel accumulation adds one partial sum per BATCH GROUP (16 or 32 rows) to each element with a
-        # float atomic: with <= 2 groups (B <= 32, every BASELINE workload) the result does not depend on the
-        # arrival order (a + b == b + a, the first add lands on an exact 0), i.e. it is bit-reproducible;
-        # with more groups the order would matter, so those shapes take the deterministic column-sum pass.
-        db_in_kernel = ctx.has_bias and B <= 32
-        # the input-gradient GEMM dX = dG [W_ih_f; W_ih_r] multiplies dG as its row-major A panel, the weight-gradient GEMMs
-        # multiply dG^T as theirs: the BPTT kernel writes both itself where its plan can (bf16x6) and the GEMMs run in
-        # stream order (the wide layers; side-stream consumers would outlive the pooled buffer)
-        bf_bwd = bool(_REC_PANELS and L.asrk_lstm_plan_is_bf(T, B, H, ndir, 1, rec_flags(1)))
-        pG = pGT = None
-        if (bf_bwd and ctx.needs_input_grad[0] and w_stack is not None and ndir * 4 * H == 8 * H and
-                gemm_takes_split(M, Din, 8 * H)):
-            pG = _BlankPanel.take(M, 8 * H, dev)
-            _panel_state["stats"]["dg"] += pG is not None
-        share0 = (_os.environ.get("ASRK_SHARE_PANELS", "1") != "0" and T > 1 and H % 128 == 0 and B % 8 == 0 and
-                  gemm_takes_split(4 * H, H, (T - 1) * B))
-        if bf_bwd and share0 and B % 16 == 0 and not _defer_beside_bptt() and ldg == ndir * 4 * H:
-            pGT = _BlankPanel.take(ndir * 4 * H, M, dev)
-            _panel_state["stats"]["dgt"] = _panel_state["stats"].get("dgt", 0) + (pGT is not None)
+        needs_dx = ctx.needs_input_grad[0]
         w_ih, w_hh = (w_ih_f, w_ih_r), (w_hh_f, w_hh_r)
-        # both directions' dW_ih share one launch only when they are computed on the same stream - and only into
-        # scratch: with a data-parallel engine each direction's GEMM writes its rows straight into that weight's slice
-        # of the gradient bucket (two launches of 4H rows: still >= 2 full rounds of tiles on the wide layers)
-        can_defer = _can_defer(w_ih_f, w_hh_f, w_ih_r, w_hh_r, *ctx.bias_refs)
-        to_scratch = not grad_has_destination(*w_ih[:ndir])
-        stack_dw = (ctx.needs_input_grad[0] or not can_defer) and to_scratch
-        rows_ih = 8 * H if (w_stack is not None and stack_dw) else 4 * H
-        # A NARROW input (cfg3's bottom layer: Din = 80) leaves dW_ih = dG^T X too few output tiles for the split GEMM's
-        # routing rule, yet its K is as deep as the wide layers': it multiplies the dG^T panel too, K cut into slices
-        # that a second kernel sums in a fixed order, one launch over both directions' rows where the result goes to
-        # scratch.  (Until round 6 it ran as exact-f32 GEMMs that read the f32 dG again: 3.4 ms of kernels per cfg3 step.)
-        narrow_ih = pGT is not None and Din % 4 == 0 and not gemm_takes_split(rows_ih, Din, M)
-        if narrow_ih and w_stack is not None and to_scratch:
-            rows_ih = 8 * H
-        # Does anything read the f32 dG?  Not when every weight gradient multiplies dG^T (with pGT every path below runs
-        # param_grads_panels; dW_ih takes panels when Din % 4 == 0), dX is not wanted or multiplies the dG panel, and the
-        # bias gradient was summed in the kernel: then the kernel keeps its four 4-byte stores per cell and step.
-        skip_dg = (_REC_SKIP_DG and pGT is not None and Din % 4 == 0 and (not ctx.needs_input_grad[0] or pG is not None)
-                   and (db_in_kernel or not ctx.has_bias))
-        if pG is not None or pGT is not None:
-            _panel_state["stats"]["no_dg"] = _panel_state["stats"].get("no_dg", 0) + skip_dg
-            _lib.check(L.asrk_lstm_rec_bwd_pyr_panel_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(C), _p(dYc), T, B, H,
-                                                         ndir, _p(xc_.buf), xc_.prefilled, _p(ws),
-                                                         _p(db_all if db_in_kernel else None), mode, rate,
-                                                         _p(pG.buf if pG is not None else None),
-                                                         _p(pGT.buf if pGT is not None else None),
-                                                         xc_.flags | (ASRK_REC_BWD_NO_DG if skip_dg else 0), _stream()),
-                       "lstm_rec_bwd")
-        else:
-            _lib.check(L.asrk_lstm_rec_bwd_pyr_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(C), _p(dYc), T, B, H,
-                                                   ndir, _p(xc_.buf), xc_.prefilled, _p(ws),
-                                                   _p(db_all if db_in_kernel else None), mode, rate,
-                                                   xc_.flags, _stream()), "lstm_rec_bwd")
-        xc_.done()
-        if ctx.has_bias and not db_in_kernel:
-            colsum(G, M, ndir * 4 * H, ndir * 4 * H, db_all)
-        _gemm_phase_begins()
+        # G (activated gates) -> dG (pre-activation gradients), in place.  The facts are gathered inside the frame:
+        # _defer_beside_bptt() answers for the BPTT plan that _bptt_launch has just noted.
+        with _bptt_launch(L, T, B, H, ndir, ctx.has_bias, G, dev) as (xc_, db_all):
+            plan = lstm_bwd_plan(T, B, Din, H, ndir, ctx.has_bias, needs_dx, w_stack is not None,
+                                 _can_defer(w_ih_f, w_hh_f, w_ih_r, w_hh_r, *ctx.bias_refs),
+                                 not grad_has_destination(*w_ih[:ndir]), _defer_beside_bptt(),
+                                 bool(_REC_PANELS and L.asrk_lstm_plan_is_bf(T, B, H, ndir, 1, rec_flags(1))),
+                                 _os.environ.get("ASRK_SHARE_PANELS", "1") != "0", _REC_SKIP_DG, gemm_takes_split,
+                                 lambda rows, K: _BlankPanel.take(rows, K, dev))
+            pG, pGT = plan.pG, plan.pGT
+            stats = _panel_state["stats"]
+            stats["dg"] += pG is not None
+            stats["dgt"] += pGT is not None
+            stats["no_dg"] += plan.skip_dg
+            stats["dw_ih_splitk"] += (plan.dw_ih_route == IH_SPLITK) * (1 if plan.rows_ih == 8 * H else ndir)
+            db = db_all if plan.db_in_kernel else None
+            if pG is not None or pGT is not None:
+                _lib.check(L.asrk_lstm_rec_bwd_pyr_panel_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(C), _p(dYc), T, B, H,
+                                                             ndir, _p(xc_.buf), xc_.prefilled, _p(ws), _p(db), mode, rate,
+                                                             _p(pG.buf if pG is not None else None),
+                                                             _p(pGT.buf if pGT is not None else None),
+                                                             xc_.flags | (ASRK_REC_BWD_NO_DG if plan.skip_dg else 0),
+                                                             _stream()), "lstm_rec_bwd")
+            else:
+                _lib.check(L.asrk_lstm_rec_bwd_pyr_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(C), _p(dYc), T, B, H,
+                                                       ndir, _p(xc_.buf), xc_.prefilled, _p(ws), _p(db), mode, rate,
+                                                       xc_.flags, _stream()), "lstm_rec_bwd")
         dG = G
         f32 = dict(dtype=torch.float32, device=dev)
         dx = None
-        if ctx.needs_input_grad[0]:
+        if needs_dx:
             dx = torch.empty((M, Din), **f32)
             if pG is not None:            # dG arrived as a panel: only the (transposed) weight stack is split here
                 pWT = SplitPanel(w_stack, Din, Din, 8 * H, True)
@@ -1009,14 +1085,8 @@ class LSTMLayerFn(Function):
                 if ndir == 2:
                     gemm(0, 0, M, Din, 4 * H, dG[:, 4 * H:], ldg, w_ih_r, Din, dx, Din, beta=1.0)
             dx = dx.view(T, B, Din)
-        dw_ih_stack = [None]
-        # Weight gradients contract over the tokens with dG^T as the left operand three times (dW_ih, dW_hh of
-        # both directions): on the split-GEMM path dG^T (and Y^T, X^T) are split ONCE into bf16 panels and the
-        # GEMMs take row / k ranges of them.  Needs every direction's GEMMs on one stream (share[1]).
-        share = [share0, False]
-        panels = {}
-        if pGT is not None:
-            panels["dGT"] = pGT               # written by the BPTT kernel: no transposed split pass over dG
+        panels = {} if pGT is None else {"dGT": pGT}      # written by the BPTT kernel: no transposed split pass over dG
+        dw_ih_stack = []         # the stacked dW_ih [8H, Din]: one launch, on the stream of the direction that runs first
 
         def panel(name, src, ld, rows):
             if name not in panels:
@@ -1025,110 +1095,70 @@ class LSTMLayerFn(Function):
 
         def dg_gemm(Mo, No, Ko, m0, k0, pB, b_row0, b_k0, out, ldo, splitk=None):
             """out[Mo, No] = dG[k0 : k0 + Ko, m0 : m0 + Mo]^T  B-panel rows, through the transposed panel dG^T"""
-            gemm_panels(Mo, No, Ko, panel("dGT", dG, ldg, ndir * 4 * H), m0, k0, pB, b_row0, b_k0, out, ldo,
-                        splitk=splitk)
+            gemm_panels(Mo, No, Ko, panel("dGT", dG, ldg, ldg), m0, k0, pB, b_row0, b_k0, out, ldo, splitk=splitk)
 
-        def param_grads_panels(d):
-            pY = panel("YT", Y, ldy, ndir * H)
-            Mh = (T - 1) * B
-            dw_hh = grad_out(w_hh[d], (4 * H, H), dev)
-            # direction 0: dG rows of t >= 1 against Y[t-1]; direction 1: dG rows of t <= T-2 against Y[t+1]
-            dg_gemm(4 * H, H, Mh, d * 4 * H, B if d == 0 else 0, pY, d * H, 0 if d == 0 else B, dw_hh, H)
-            if (gemm_takes_split(rows_ih, Din, M) or narrow_ih) and Din % 4 == 0:
-                pX = panel("XT", xc, Din, Din)
-                sk = 0 if narrow_ih else None                # narrow: fixed-order split-K, slice count by the library
-                if rows_ih == 8 * H:
-                    if dw_ih_stack[0] is None:
-                        dw_ih_stack[0] = torch.empty((8 * H, Din), **f32)
-                        dg_gemm(8 * H, Din, M, 0, 0, pX, 0, 0, dw_ih_stack[0], Din, sk)
-                        _panel_state["stats"]["dw_ih_splitk"] = _panel_state["stats"].get("dw_ih_splitk", 0) + narrow_ih
-                    dw_ih = dw_ih_stack[0][d * 4 * H:(d + 1) * 4 * H]
-                else:
-                    dw_ih = grad_out(w_ih[d], (4 * H, Din), dev)
-                    dg_gemm(4 * H, Din, M, d * 4 * H, 0, pX, 0, 0, dw_ih, Din, sk)
-                    _panel_state["stats"]["dw_ih_splitk"] = _panel_state["stats"].get("dw_ih_splitk", 0) + narrow_ih
-            elif rows_ih == 8 * H:
-                if dw_ih_stack[0] is None:
-                    dw_ih_stack[0] = torch.empty((8 * H, Din), **f32)
-                    gemm(1, 0, 8 * H, Din, M, dG, ldg, xc, Din, dw_ih_stack[0], Din)
-                dw_ih = dw_ih_stack[0][d * 4 * H:(d + 1) * 4 * H]
+        def dw_ih_of(d):
+            stacked = plan.rows_ih == 8 * H
+            if not (stacked and dw_ih_stack):
+                out = torch.empty((8 * H, Din), **f32) if stacked else grad_out(w_ih[d], (4 * H, Din), dev)
+                m0 = 0 if stacked else d * 4 * H
+                if plan.dw_ih_route == IH_F32:
+                    gemm(1, 0, plan.rows_ih, Din, M, dG[:, m0:], ldg, xc, Din, out, Din)
+                else:                     # splitk = 0: K cut into slices summed in a fixed order, their count by the library
+                    dg_gemm(plan.rows_ih, Din, M, m0, 0, panel("XT", xc, Din, Din), 0, 0, out, Din,
+                            0 if plan.dw_ih_route == IH_SPLITK else None)
+                if not stacked:
+                    return out
+                dw_ih_stack.append(out)
+            return dw_ih_stack[0][d * 4 * H:(d + 1) * 4 * H]
+
+        def dw_hh_of(d):
+            if T <= 1:
+                return zeros((4 * H, H), dev)
+            out, Mh = grad_out(w_hh[d], (4 * H, H), dev), (T - 1) * B
+            # direction 0: dG rows of t >= 1 against h_{t-1} = Y[t-1]; direction 1 (reverse): rows of t <= T-2 against Y[t+1]
+            if plan.dw_hh_panels:
+                dg_gemm(4 * H, H, Mh, d * 4 * H, B if d == 0 else 0, panel("YT", Y, ldy, ldy), d * H, 0 if d == 0 else B,
+                        out, H)
+            elif d == 0:
+                gemm(1, 0, 4 * H, H, Mh, dG[B:], ldg, Y, ldy, out, H)
             else:
-                dw_ih = grad_out(w_ih[d], (4 * H, Din), dev)
-                gemm(1, 0, 4 * H, Din, M, dG[:, d * 4 * H:], ldg, xc, Din, dw_ih, Din)
-            db = db2 = None
-            if ctx.has_bias:
-                db = db_all[d]
-                db2 = db.clone()
-            return dw_ih, dw_hh, db, db2
+                gemm(1, 0, 4 * H, H, Mh, dG[:, 4 * H:], ldg, Y[B:, H:], ldy, out, H)
+            return out
 
         def param_grads(d):
-            if share[0] and share[1]:
-                return param_grads_panels(d)
-            dGd = dG[:, d * 4 * H:]
-            if w_stack is not None and stack_dw:
-                if dw_ih_stack[0] is None:    # dW_ih of both directions: one GEMM with M = 8H
-                    dw_ih_stack[0] = torch.empty((8 * H, Din), **f32)
-                    gemm(1, 0, 8 * H, Din, M, dG, ldg, xc, Din, dw_ih_stack[0], Din)
-                dw_ih = dw_ih_stack[0][d * 4 * H:(d + 1) * 4 * H]
+            # launch order: where dW_hh multiplies panels it goes first (Y^T and dG^T are split before X^T)
+            if plan.dw_hh_panels:
+                dw_hh = dw_hh_of(d)
+                dw_ih = dw_ih_of(d)
             else:
-                dw_ih = grad_out(w_ih[d], (4 * H, Din), dev)
-                gemm(1, 0, 4 * H, Din, M, dGd, ldg, xc, Din, dw_ih, Din)
-            dw_hh = zeros((4 * H, H), dev) if T <= 1 else grad_out(w_hh[d], (4 * H, H), dev)
-            if T > 1:
-                Mh = (T - 1) * B
-                if d == 0:   # h_{t-1} = Y[t-1]
-                    gemm(1, 0, 4 * H, H, Mh, dGd[B:], ldg, Y, ldy, dw_hh, H)
-                else:        # reverse direction: previous state of t is Y[t+1]
-                    gemm(1, 0, 4 * H, H, Mh, dGd, ldg, Y[B:, H:], ldy, dw_hh, H)
+                dw_ih = dw_ih_of(d)
+                dw_hh = dw_hh_of(d)
             db = db2 = None
             if ctx.has_bias:
                 db = db_all[d]
                 db2 = db.clone()
             return dw_ih, dw_hh, db, db2
 
-        beside = _defer_beside_bptt() or not ctx.needs_input_grad[0]
-        if can_defer and beside:
-            # off the critical path: the next layer's BPTT does not need dW / db
-            if ctx.needs_input_grad[0] or ndir == 1:
-                with _SideStream(dev, (dG, xc, Y, db_all)) as side:
-                    share[1] = True
-                    grads = [param_grads(d) for d in range(ndir)]
-                    side.keep(*[t for g in grads for t in g])
-            elif pGT is not None and Din % 4 == 0:
-                # bottom layer with the dG^T panel from the kernel: every weight gradient multiplies panels (dW_ih with a
-                # wide input like the layers above, with a narrow one through the split-K launch) and fills the chip on
-                # its own - stream order.  (Until round 6 the narrow-input case ran its directions on two streams beside
-                # each other for the sake of the small f32 dW_ih GEMMs; the 256-tile dW_hh launches only serialised there.)
-                share[1] = True
-                grads = [param_grads(d) for d in range(ndir)]
-            elif pGT is not None:
-                # the same with an input width no panel takes (Din % 4 != 0): dW_hh multiplies row ranges of the ONE dG^T
-                # panel (and of Y^T, split here before the streams fork), dW_ih reads the f32 dG; the directions run side
-                # by side, the pooled panel goes back at the end of the backward pass (after the streams re-join)
-                pY = panel("YT", Y, ldy, ndir * H)
-                share[1] = True
-                with _SideStream(dev, (dG, xc, Y, db_all, pGT.buf, pY.buf), background=False) as side:
-                    g1 = param_grads(1)
-                    side.keep(*g1)
-                grads = [param_grads(0), g1]
-                _defer["release"].append(pGT)
-                pGT = None
-            else:
-                # bottom layer (no input gradient wanted): no BPTT follows, nothing to hide behind.
-                # Its small GEMMs (dW_ih with Din = 80, column sums) leave CUs idle one at a time, so
-                # the two directions run side by side: reverse on the side stream, forward here.
-                with _SideStream(dev, (dG, xc, Y, db_all), background=False) as side:
-                    g1 = param_grads(1)
-                    side.keep(*g1)
-                grads = [param_grads(0), g1]
-        else:
-            share[1] = True
+        if plan.schedule == STREAM:
             grads = [param_grads(d) for d in range(ndir)]
+        elif plan.schedule == SIDE_ALL:
+            with _SideStream(dev, (dG, xc, Y, db_all)) as side:
+                grads = [param_grads(d) for d in range(ndir)]
+                side.keep(*[t for g in grads for t in g])
+        else:
+            inputs = (dG, xc, Y, db_all)
+            if plan.schedule == SIDE_REVERSE_SHARED:
+                inputs += (pGT.buf, panel("YT", Y, ldy, ldy).buf)         # Y^T: split here, before the streams fork
+            with _SideStream(dev, inputs, background=False) as side:
+                g1 = param_grads(1)
+                side.keep(*g1)
+            grads = [param_grads(0), g1]
         if pGT is not None:
-            if share[1] and not _defer["pending"]:
-                pGT.release()                 # every consumer was enqueued on this stream
+            if plan.defer_release or _defer["pending"]:
+                _defer["release"].append(pGT)     # side-stream GEMMs may still read it: back at the end of the backward pass
             else:
-                _defer["release"].append(pGT)
+                pGT.release()                     # every consumer was enqueued on this stream
         if ndir == 1:
             grads.append((None, None, None, None))
         return (dx,) + grads[0] + grads[1] + (None, None)
@@ -1221,12 +1251,7 @@ def lstm_layer_packed(x_tm, params_f, params_r, lens, pyramid=None):
     Y = zeros((M, ndir * H), dev)
     C = torch.empty((M, ndir * H), dtype=torch.float32, device=dev)
     rate, style = pyramid if pyramid is not None else (1, None)
-    mode = {None: 0, 'concat': 1, 'drop': 2}[style if rate > 1 else None]
-    Y2 = None
-    if mode == 1:
-        Y2 = zeros((T // rate, B, rate * ndir * H), dev)
-    elif mode == 2:
-        Y2 = zeros(((T + rate - 1) // rate, B, ndir * H), dev)
+    mode, Y2 = _pyramid_out(T, B, ndir * H, rate, style, dev, zero=True)
     ws = lstm_workspace(dev)
     xc_ = _Exchange(L, T, B, H, ndir, 0, dev)
     _lib.check(L.asrk_lstm_rec_fwd_len_f32(_p(G), _p(w_hh_f), _p(w_hh_r), _p(Y), _p(C), _p(lens_d), T, B, H, ndir,

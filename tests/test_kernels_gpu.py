@@ -502,9 +502,9 @@ def test_producer_written_panels_equal_split_passes(ops, T, B, H, pyr, xgrad):
     panel holds the same three bf16 planes the split pass would write, so a two-layer stack gives BIT-IDENTICAL outputs
     with the feature on and off (the gradients pass through GEMMs whose split-K sums meet in atomics: 1e-5).  H = 1024:
     the second layer multiplies the first one's panel, its BPTT writes the dG panel, and both layers' BPTT write dG^T
-    (the weight gradients' left operand) - xgrad = False makes the first layer the BOTTOM layer, whose two directions'
-    weight-gradient GEMMs share that one panel across two streams; H = 512 (no stacked-direction GEMM to take a panel):
-    emitted on request, dropped unused, same results."""
+    (the weight gradients' left operand) - xgrad = False makes the first layer the BOTTOM layer, whose weight-gradient
+    GEMMs all multiply that one panel in stream order (D = 256: dW_ih takes panels too); H = 512 (no stacked-direction
+    GEMM to take a panel): emitted on request, dropped unused, same results."""
     g = torch.Generator().manual_seed(T + H)
     D = 256
     x = torch.randn(T, B, D, generator=g).to(DEV)

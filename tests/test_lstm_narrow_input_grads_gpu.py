@@ -6,7 +6,9 @@
  * every consumer of dG then takes a panel, so the BPTT launch carries ASRK_REC_BWD_NO_DG and does not store the f32 dG
    (ops._REC_SKIP_DG turns that off);
  * wide input with an input gradient (Din = 2048): dX multiplies the dG panel, the weight gradients dG^T - the flag is set
-   together with both panels.
+   together with both panels;
+ * an input width no panel takes (Din = 38): the two directions' dW_hh share the one dG^T panel across two streams, dW_ih
+   and with it the f32 dG stay.
 
 T = 12, B = 32 (two 16-row batch groups), H = 1024: the smallest shapes at which the bf16x6 BPTT plan writes panels
 (384 tokens = 12 k-tiles, three row tiles of X^T padding for Din < 128)."""
@@ -116,6 +118,30 @@ def test_narrow_input_dw_ih_through_splitk_panels(ops, Din):
     close(out[True], out[False])
     for u, v in zip(out[True], out[False]):
         assert torch.equal(u, v)
+    ops.drop_exchange_pool()
+
+
+def test_odd_input_width_shares_the_panel_across_streams(ops):
+    """Din = 38 (no panel takes an input width that is no multiple of 4), no input gradient: dW_hh of both directions
+    multiplies row ranges of the ONE dG^T panel the kernel wrote, the reverse direction on the side stream, dW_ih reads
+    the f32 dG (so the kernel keeps storing it) - and the pooled panel goes back only when the backward pass ends."""
+    Din = 38
+    x0, p0, dy = make(Din, 100 + Din)
+    ref = reference(ops, x0, p0, dy, False)
+    ops.drop_exchange_pool()
+    fresh_pools(ops)
+    s0 = dict(ops._panel_state["stats"])
+    out, st = passes(ops, x0, p0, dy, False, 3)
+    st = [s0] + st
+    assert counters(st, "dgt") == [s0.get("dgt", 0) + i for i in (0, 0, 1, 2)]
+    assert counters(st, "no_dg") == [s0.get("no_dg", 0)] * 4
+    assert counters(st, "dw_ih_splitk") == [s0.get("dw_ih_splitk", 0)] * 4
+    close(out, ref)
+    pools_armed(ops)
+    ops.check_errors()
+    # the backward pass has ended and joined its side stream: nothing waits for release, the panel is back in the pool
+    assert ops._defer["release"] == []
+    assert [len(v) for k, v in ops._panel_pool["free"].items() if k[2:] == (8 * H, T * B)] == [1]
     ops.drop_exchange_pool()
 
 
