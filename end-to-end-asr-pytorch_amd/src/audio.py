@@ -391,11 +391,14 @@ def load_pcm(filepath):
 
 class BatchFeatureTransform:
     """The reference's per-file transform (create_transform: ExtractAudioFeature -> Delta -> CMVN -> Postprocess,
-    src/audio.py:115-133) followed by pad_sequence (src/data.py:39) for a WHOLE BATCH in 7 launches: padded
-    PCM [B, Nmax] -> frames of all utterances stacked [sum m, 400] -> one DFT GEMM -> power -> one mel GEMM ->
-    log -> delta + CMVN + layout + zero padding in one kernel -> (feat [B, Tmax, (order+1)*D], feat_len [B]).
-    Same arithmetic per frame as the per-file modules (the framing kernel is the same code; CMVN sums in a
-    different order: agreement ~1e-6)."""
+    src/audio.py:115-133) followed by pad_sequence (src/data.py:39) for a WHOLE BATCH in two launches: padded
+    PCM [B, Nmax] (int16 or float32) -> log-mel energies of all utterances stacked [sum m, D] in the fused kernel
+    (framing, FFT in LDS, power, mel weights, log; FFT sizes 256, 512, 1024) -> delta + CMVN + layout + zero padding in
+    one kernel -> (feat [B, Tmax, (order+1)*D], feat_len [B]).  FFT sizes outside 256..1024 take the unfused route
+    instead of the first launch: batched framing kernel -> DFT GEMM -> power -> mel GEMM -> log; mfcc adds one DCT
+    GEMM; speed factors one resampling launch in front.  Same arithmetic per frame as the per-file modules (the
+    framing is the same code; CMVN sums in a different order: agreement ~1e-6).  Delta filters of up to 15 taps
+    (17 and more raise NotImplementedError; create_transform then serves the per-file chain alone)."""
 
     def __init__(self, audio_config, device='cuda'):
         cfg = dict(audio_config)
