@@ -75,6 +75,13 @@ SIGNATURES = {
                                           c_vp]),
     "asrk_fbank_logmel_batch_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_int, c_int, c_vp, c_int, c_int, c_int, c_f32, c_f32, c_int, c_f32, c_vp]),
+    "asrk_fbank_frames_dither_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_int, c_f32,
+                                             ctypes.c_uint64, c_vp]),
+    "asrk_fbank_frames_batch_dither_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int,
+                                                   c_int, c_int, c_f32, c_f32, c_int, c_f32, c_vp, c_vp]),
+    "asrk_fbank_logmel_batch_dither_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                                                   c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_f32, c_f32, c_int,
+                                                   c_f32, c_f32, c_vp, c_vp]),
     "asrk_spec_augment_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_f32,
                                       c_vp]),
     "asrk_resample_rows_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_i64,

@@ -11,19 +11,70 @@
 //   delta    : 9-tap / 5-tap cross-correlation along time with ZERO padding (src/audio.py:48-54)
 //   cmvn     : per (channel, feature) row over time, unbiased std, eps added to std (audio.py:24-27)
 // All of these are HBM-streaming kernels apart from the two GEMMs.
+//
+// Dither (the reference's `audio.dither` key; torchaudio adds randn * dither to the strided frame matrix): the DITHER
+// instantiations of the three framing kernels work on v[f][j] = x[f*shift + j] + dither * z(key, f, j) instead of x,
+// z the pure noise function of include/asrk.h (philox.h).  The plain instantiations hold no trace of it.
 #include "common.h"
+#include "philox.h"
+#include <cmath>
 
 namespace {
 
+// One frame of the unfused dithered route, one wave: lane owns the position groups g = lane, lane + 64, .. (four
+// positions, one Philox call).  Nothing is staged (a frame has no size limit here): with DC removal the normals are
+// drawn a second time for the mean; the predecessor of a group's first position comes from the neighbouring lane.
+template <typename SampleT>
+__device__ __forceinline__ void dither_frame_row(const SampleT *__restrict__ x, const float *__restrict__ window,
+                                                 float *__restrict__ o, int win, int ldf, float scale, float preemph,
+                                                 int remove_dc, float dither, uint64_t key, int f, int lane) {
+    float mean = 0.f;
+    if (remove_dc) {
+        float s = 0.f;
+        for (int g = lane; 4 * g < win; g += 64) {
+            float z[4];
+            dither_normals(key, (uint32_t)f, (uint32_t)g, z);
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+                if (4 * g + h < win) s += (float)x[4 * g + h] * scale + dither * z[h];
+        }
+        mean = wave_sum(s) / (float)win;
+    }
+    float carry = 0.f;                                   // v[4 * g0 - 1]: the last position of the previous 256
+    for (int g0 = 0; 4 * g0 < ldf; g0 += 64) {           // wave-uniform trip count: every lane takes part in the shuffles
+        const int g = g0 + lane;
+        float z[4], v[4];
+        dither_normals(key, (uint32_t)f, (uint32_t)g, z);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) v[h] = 4 * g + h < win ? (float)x[4 * g + h] * scale + dither * z[h] : 0.f;
+        const float up = __shfl_up(v[3], 1, 64);
+        float prev = lane ? up : carry;
+        if (g == 0) prev = v[0];                         // replicate-padded first sample
+        carry = __shfl(v[3], 63, 64);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int j = 4 * g + h;
+            if (j < ldf) o[j] = j < win ? ((v[h] - mean) - preemph * (prev - mean)) * window[j] : 0.f;
+            prev = v[h];
+        }
+    }
+}
+
 // one wave per frame; frames: [m, ldf] (ldf >= win, multiple of 4; pad columns zeroed)
+template <bool DITHER>
 __global__ __launch_bounds__(256) void fbank_frames_kernel(const float *__restrict__ wavef,
                                                            const float *__restrict__ window,
                                                            float *__restrict__ frames, int64_t n_samples,
                                                            int m, int win, int shift, int ldf,
-                                                           float preemph, int remove_dc) {
+                                                           float preemph, int remove_dc, float dither, uint64_t key) {
     const int f = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (f >= m) return;
     const float *x = wavef + (int64_t)f * shift;
+    if constexpr (DITHER) {
+        dither_frame_row<float>(x, window, frames + (size_t)f * ldf, win, ldf, 1.0f, preemph, remove_dc, dither, key, f,
+                                lane);
+        return;
+    }
     float s = 0.f;
     for (int j = lane; j < win; j += 64) s += x[j];
     const float mean = remove_dc ? wave_sum(s) / (float)win : 0.f;
@@ -42,17 +93,23 @@ __global__ __launch_bounds__(256) void fbank_frames_kernel(const float *__restri
 // The same framing for a whole padded batch: wave [B, ld_wave] (int16 PCM, scaled by `scale` on load - the
 // exact torchaudio.load conversion x / 32768 - or f32), frame f of utterance b goes to row frame_off[b] + f.
 // grid (ceil(max_m / 4), B); the per-frame arithmetic is the per-utterance kernel's, operation for operation.
-template <typename SampleT>
+template <typename SampleT, bool DITHER = false>
 __global__ __launch_bounds__(256) void fbank_frames_batch_kernel(const SampleT *__restrict__ wavef, int64_t ld_wave,
                                                                  const int64_t *__restrict__ frame_off,
                                                                  const float *__restrict__ window,
                                                                  float *__restrict__ frames, int win, int shift,
-                                                                 int ldf, float scale, float preemph, int remove_dc) {
+                                                                 int ldf, float scale, float preemph, int remove_dc,
+                                                                 float dither, const uint64_t *__restrict__ keys) {
     const int b = blockIdx.y;
     const int f = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int64_t off = frame_off[b];
     if (f >= (int)(frame_off[b + 1] - off)) return;
     const SampleT *x = wavef + (int64_t)b * ld_wave + (int64_t)f * shift;
+    if constexpr (DITHER) {
+        dither_frame_row<SampleT>(x, window, frames + (size_t)(off + f) * ldf, win, ldf, scale, preemph, remove_dc,
+                                  dither, keys[b], f, lane);
+        return;
+    }
     float s = 0.f;
     for (int j = lane; j < win; j += 64) s += (float)x[j] * scale;
     const float mean = remove_dc ? wave_sum(s) / (float)win : 0.f;
@@ -84,12 +141,16 @@ __global__ __launch_bounds__(256) void fbank_frames_batch_kernel(const SampleT *
 //   4. applies the triangular mel weights (bin m only touches its own [first, last) range of FFT bins; the weights
 //      come from the same dense table the GEMM used) and stores log(max(E, eps)).
 // The only global traffic is 2 B (int16) or 4 B per sample in and 4 B per mel energy out.
-template <typename SampleT, int LOG2N>
+// DITHER: the wave first writes v = x + dither * z into its SECOND tile (free until the first FFT stage; N + 2 floats
+// >= win), every normal drawn once, a lane owning whole groups of four positions; the mean, `cur` and `prev` then read
+// v from there instead of the PCM row.  No LDS is added.
+template <typename SampleT, int LOG2N, bool DITHER = false>
 __global__ __launch_bounds__(256) void fbank_logmel_batch_kernel(
     const SampleT *__restrict__ wavef, int64_t ld_wave, const int64_t *__restrict__ frame_off,
     const float *__restrict__ window, const float *__restrict__ tw_fft, const float *__restrict__ tw_unpack,
     const float *__restrict__ melT, const int *__restrict__ mel_range, int nmel, int ld_mel, float *__restrict__ out,
-    int win, int shift, float scale, float preemph, int remove_dc, float eps) {
+    int win, int shift, float scale, float preemph, int remove_dc, float eps, float dither,
+    const uint64_t *__restrict__ keys) {
     constexpr int N = 1 << LOG2N, M = N / 2, LOG2M = LOG2N - 1;     // M complex points
     constexpr int PER = M / 64;                                      // complex points per lane (M >= 64)
     __shared__ float2 s_z[4][2][M + 1];                              // per wave: ping-pong tiles (+1: X[M] / |X|^2)
@@ -104,7 +165,28 @@ __global__ __launch_bounds__(256) void fbank_logmel_batch_kernel(
     float2 *za = s_z[wave][0], *zb = s_z[wave][1];
     // ---- 1. framing (fbank_frames_batch_kernel's arithmetic)
     float sm = 0.f;
-    for (int j = lane; j < win; j += 64) sm += (float)x[j] * scale;
+    const float *vs = reinterpret_cast<const float *>(zb);
+    if constexpr (DITHER) {
+        const uint64_t key = keys[b];
+        for (int g = lane; 4 * g < win; g += 64) {       // 4 g + 3 <= N - 1: both float2 lie inside the tile
+            float z[4], v[4];
+            dither_normals(key, (uint32_t)f, (uint32_t)g, z);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                v[h] = 4 * g + h < win ? (float)x[4 * g + h] * scale + dither * z[h] : 0.f;
+                sm += v[h];
+            }
+            zb[2 * g] = make_float2(v[0], v[1]);
+            zb[2 * g + 1] = make_float2(v[2], v[3]);
+        }
+        __builtin_amdgcn_wave_barrier();
+    } else {
+        for (int j = lane; j < win; j += 64) sm += (float)x[j] * scale;
+    }
+    auto sample = [&](int j) -> float {
+        if constexpr (DITHER) return vs[j];
+        else return (float)x[j] * scale;
+    };
     const float mean = remove_dc ? wave_sum(sm) / (float)win : 0.f;
     for (int m = lane; m < M; m += 64) {
         float v[2];
@@ -113,8 +195,8 @@ __global__ __launch_bounds__(256) void fbank_logmel_batch_kernel(
             const int j = 2 * m + h;
             float r = 0.f;
             if (j < win) {
-                const float cur = (float)x[j] * scale - mean;
-                const float prev = (float)x[j > 0 ? j - 1 : 0] * scale - mean;
+                const float cur = sample(j) - mean;
+                const float prev = sample(j > 0 ? j - 1 : 0) - mean;
                 r = (cur - preemph * prev) * window[j];
             }
             v[h] = r;
@@ -355,20 +437,41 @@ inline unsigned nblk(int64_t n, int bs) { return (unsigned)asrk_div_up64(n, bs);
 
 }  // namespace
 
-extern "C" int asrk_fbank_frames_f32(const float *wave, int64_t n_samples, const float *window,
-                                     float *frames, int m, int win, int shift, int ldf,
-                                     float preemph, int remove_dc, void *stream) {
+// one validation and launch sequence behind the plain entry and the dithered one (the latter's extra refusals only
+// with `dithered`)
+static int fbank_frames_launch(const float *wave, int64_t n_samples, const float *window, float *frames, int m, int win,
+                               int shift, int ldf, float preemph, int remove_dc, bool dithered, float dither,
+                               uint64_t key, void *stream) {
     if (m < 0 || win <= 0 || shift <= 0 || ldf < win) return ASRK_EINVAL;
+    if (dithered && !(std::isfinite(dither) && dither >= 0.f)) return ASRK_EINVAL;
     if (m == 0) return ASRK_OK;
     if (!wave || !window || !frames) return ASRK_EINVAL;
     if ((int64_t)(m - 1) * shift + win > n_samples) return ASRK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     asrk_prof_begin_(PROF_FBANK, s);
-    hipLaunchKernelGGL(fbank_frames_kernel, dim3(asrk_div_up(m, 4)), dim3(256), 0, s, wave, window,
-                       frames, n_samples, m, win, shift, ldf, preemph, remove_dc);
+    if (dithered)
+        hipLaunchKernelGGL(fbank_frames_kernel<true>, dim3(asrk_div_up(m, 4)), dim3(256), 0, s, wave, window, frames,
+                           n_samples, m, win, shift, ldf, preemph, remove_dc, dither, key);
+    else
+        hipLaunchKernelGGL(fbank_frames_kernel<false>, dim3(asrk_div_up(m, 4)), dim3(256), 0, s, wave, window,
+                           frames, n_samples, m, win, shift, ldf, preemph, remove_dc, 0.f, (uint64_t)0);
     asrk_prof_end_(PROF_FBANK, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
+}
+
+extern "C" int asrk_fbank_frames_f32(const float *wave, int64_t n_samples, const float *window,
+                                     float *frames, int m, int win, int shift, int ldf,
+                                     float preemph, int remove_dc, void *stream) {
+    return fbank_frames_launch(wave, n_samples, window, frames, m, win, shift, ldf, preemph, remove_dc, false, 0.f, 0,
+                               stream);
+}
+
+extern "C" int asrk_fbank_frames_dither_f32(const float *wave, int64_t n_samples, const float *window, float *frames,
+                                            int m, int win, int shift, int ldf, float preemph, int remove_dc,
+                                            float dither, uint64_t key, void *stream) {
+    return fbank_frames_launch(wave, n_samples, window, frames, m, win, shift, ldf, preemph, remove_dc, true, dither,
+                               key, stream);
 }
 
 extern "C" int asrk_power_spectrum_f32(const float *spec, float *power, int64_t m, int nb,
@@ -425,14 +528,16 @@ extern "C" int asrk_transpose_f32(const float *x, float *y, int rows, int cols, 
     return ASRK_OK;
 }
 
-extern "C" int asrk_fbank_frames_batch_f32(const void *wave, int sample_bytes, int64_t ld_wave,
-                                           const int64_t *n_samples_host, const int64_t *frame_off, int B,
-                                           int max_m, const float *window, float *frames, int win, int shift,
-                                           int ldf, float scale, float preemph, int remove_dc, void *stream) {
+static int fbank_frames_batch_launch(const void *wave, int sample_bytes, int64_t ld_wave,
+                                     const int64_t *n_samples_host, const int64_t *frame_off, int B, int max_m,
+                                     const float *window, float *frames, int win, int shift, int ldf, float scale,
+                                     float preemph, int remove_dc, bool dithered, float dither, const uint64_t *keys,
+                                     void *stream) {
     if (B < 0 || max_m < 0 || win <= 0 || shift <= 0 || ldf < win || (sample_bytes != 2 && sample_bytes != 4))
         return ASRK_EINVAL;
+    if (dithered && !(std::isfinite(dither) && dither >= 0.f)) return ASRK_EINVAL;
     if (B == 0 || max_m == 0) return ASRK_OK;
-    if (!wave || !frame_off || !window || !frames) return ASRK_EINVAL;
+    if (!wave || !frame_off || !window || !frames || (dithered && !keys)) return ASRK_EINVAL;
     // the frames of every utterance must lie inside its row of the padded batch
     if ((int64_t)(max_m - 1) * shift + win > ld_wave) return ASRK_EINVAL;
     if (n_samples_host)
@@ -441,14 +546,82 @@ extern "C" int asrk_fbank_frames_batch_f32(const void *wave, int sample_bytes, i
     hipStream_t s = (hipStream_t)stream;
     asrk_prof_begin_(PROF_FBANK, s);
     const dim3 grid(asrk_div_up(max_m, 4), B);
-    if (sample_bytes == 2)
-        hipLaunchKernelGGL(fbank_frames_batch_kernel<int16_t>, grid, dim3(256), 0, s,
-                           reinterpret_cast<const int16_t *>(wave), ld_wave, frame_off, window, frames, win, shift,
-                           ldf, scale, preemph, remove_dc);
-    else
-        hipLaunchKernelGGL(fbank_frames_batch_kernel<float>, grid, dim3(256), 0, s,
-                           reinterpret_cast<const float *>(wave), ld_wave, frame_off, window, frames, win, shift, ldf,
-                           scale, preemph, remove_dc);
+#define ASRK_FRAMES_ARGS(T_)                                                                                       \
+    grid, dim3(256), 0, s, reinterpret_cast<const T_ *>(wave), ld_wave, frame_off, window, frames, win, shift, ldf, \
+        scale, preemph, remove_dc, dither, keys
+    if (dithered) {
+        if (sample_bytes == 2) hipLaunchKernelGGL((fbank_frames_batch_kernel<int16_t, true>), ASRK_FRAMES_ARGS(int16_t));
+        else hipLaunchKernelGGL((fbank_frames_batch_kernel<float, true>), ASRK_FRAMES_ARGS(float));
+    } else {
+        if (sample_bytes == 2) hipLaunchKernelGGL(fbank_frames_batch_kernel<int16_t>, ASRK_FRAMES_ARGS(int16_t));
+        else hipLaunchKernelGGL(fbank_frames_batch_kernel<float>, ASRK_FRAMES_ARGS(float));
+    }
+#undef ASRK_FRAMES_ARGS
+    asrk_prof_end_(PROF_FBANK, s);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+extern "C" int asrk_fbank_frames_batch_f32(const void *wave, int sample_bytes, int64_t ld_wave,
+                                           const int64_t *n_samples_host, const int64_t *frame_off, int B,
+                                           int max_m, const float *window, float *frames, int win, int shift,
+                                           int ldf, float scale, float preemph, int remove_dc, void *stream) {
+    return fbank_frames_batch_launch(wave, sample_bytes, ld_wave, n_samples_host, frame_off, B, max_m, window, frames,
+                                     win, shift, ldf, scale, preemph, remove_dc, false, 0.f, nullptr, stream);
+}
+
+extern "C" int asrk_fbank_frames_batch_dither_f32(const void *wave, int sample_bytes, int64_t ld_wave,
+                                                  const int64_t *n_samples_host, const int64_t *frame_off, int B,
+                                                  int max_m, const float *window, float *frames, int win, int shift,
+                                                  int ldf, float scale, float preemph, int remove_dc, float dither,
+                                                  const uint64_t *keys, void *stream) {
+    return fbank_frames_batch_launch(wave, sample_bytes, ld_wave, n_samples_host, frame_off, B, max_m, window, frames,
+                                     win, shift, ldf, scale, preemph, remove_dc, true, dither, keys, stream);
+}
+
+static int fbank_logmel_batch_launch(const void *wave, int sample_bytes, int64_t ld_wave,
+                                     const int64_t *n_samples_host, const int64_t *frame_off, int B, int max_m,
+                                     const float *window, const float *tw_fft, const float *tw_unpack,
+                                     const float *melT, const int *mel_range, int nmel, int ld_mel, float *mel, int win,
+                                     int shift, int log2n, float scale, float preemph, int remove_dc, float eps,
+                                     bool dithered, float dither, const uint64_t *keys, void *stream) {
+    if (B < 0 || max_m < 0 || win <= 0 || shift <= 0 || nmel <= 0 || ld_mel < nmel ||
+        (sample_bytes != 2 && sample_bytes != 4))
+        return ASRK_EINVAL;
+    if (dithered && !(std::isfinite(dither) && dither >= 0.f)) return ASRK_EINVAL;
+    if (log2n < 8 || log2n > 10 || win > (1 << log2n)) return ASRK_ESHAPE;
+    if (B == 0 || max_m == 0) return ASRK_OK;
+    if (!wave || !frame_off || !window || !tw_fft || !tw_unpack || !melT || !mel_range || !mel || (dithered && !keys))
+        return ASRK_EINVAL;
+    if ((int64_t)(max_m - 1) * shift + win > ld_wave) return ASRK_EINVAL;
+    if (n_samples_host)
+        for (int b = 0; b < B; ++b)
+            if (n_samples_host[b] > ld_wave) return ASRK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    asrk_prof_begin_(PROF_FBANK, s);
+    const dim3 grid(asrk_div_up(max_m, 4), B);
+#define ASRK_FBANK_ARGS(T_)                                                                                        \
+    grid, dim3(256), 0, s, reinterpret_cast<const T_ *>(wave), ld_wave, frame_off, window, tw_fft, tw_unpack, melT, \
+        mel_range, nmel, ld_mel, mel, win, shift, scale, preemph, remove_dc, eps, dither, keys
+#define ASRK_FBANK_CASE(L2_)                                                                                       \
+    case L2_:                                                                                                      \
+        if (dithered) {                                                                                            \
+            if (sample_bytes == 2)                                                                                 \
+                hipLaunchKernelGGL((fbank_logmel_batch_kernel<int16_t, L2_, true>), ASRK_FBANK_ARGS(int16_t));     \
+            else                                                                                                   \
+                hipLaunchKernelGGL((fbank_logmel_batch_kernel<float, L2_, true>), ASRK_FBANK_ARGS(float));         \
+        } else {                                                                                                   \
+            if (sample_bytes == 2)                                                                                 \
+                hipLaunchKernelGGL((fbank_logmel_batch_kernel<int16_t, L2_>), ASRK_FBANK_ARGS(int16_t));           \
+            else                                                                                                   \
+                hipLaunchKernelGGL((fbank_logmel_batch_kernel<float, L2_>), ASRK_FBANK_ARGS(float));               \
+        }                                                                                                          \
+        break;
+    switch (log2n) {
+        ASRK_FBANK_CASE(8) ASRK_FBANK_CASE(9) ASRK_FBANK_CASE(10)
+    }
+#undef ASRK_FBANK_CASE
+#undef ASRK_FBANK_ARGS
     asrk_prof_end_(PROF_FBANK, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
@@ -460,39 +633,21 @@ extern "C" int asrk_fbank_logmel_batch_f32(const void *wave, int sample_bytes, i
                                            const float *melT, const int *mel_range, int nmel, int ld_mel, float *mel,
                                            int win, int shift, int log2n, float scale, float preemph, int remove_dc,
                                            float eps, void *stream) {
-    if (B < 0 || max_m < 0 || win <= 0 || shift <= 0 || nmel <= 0 || ld_mel < nmel ||
-        (sample_bytes != 2 && sample_bytes != 4))
-        return ASRK_EINVAL;
-    if (log2n < 8 || log2n > 10 || win > (1 << log2n)) return ASRK_ESHAPE;
-    if (B == 0 || max_m == 0) return ASRK_OK;
-    if (!wave || !frame_off || !window || !tw_fft || !tw_unpack || !melT || !mel_range || !mel) return ASRK_EINVAL;
-    if ((int64_t)(max_m - 1) * shift + win > ld_wave) return ASRK_EINVAL;
-    if (n_samples_host)
-        for (int b = 0; b < B; ++b)
-            if (n_samples_host[b] > ld_wave) return ASRK_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    asrk_prof_begin_(PROF_FBANK, s);
-    const dim3 grid(asrk_div_up(max_m, 4), B);
-#define ASRK_FBANK_CASE(L2_)                                                                                       \
-    case L2_:                                                                                                      \
-        if (sample_bytes == 2)                                                                                     \
-            hipLaunchKernelGGL((fbank_logmel_batch_kernel<int16_t, L2_>), grid, dim3(256), 0, s,                   \
-                               reinterpret_cast<const int16_t *>(wave), ld_wave, frame_off, window, tw_fft,        \
-                               tw_unpack, melT, mel_range, nmel, ld_mel, mel, win, shift, scale, preemph,          \
-                               remove_dc, eps);                                                                    \
-        else                                                                                                       \
-            hipLaunchKernelGGL((fbank_logmel_batch_kernel<float, L2_>), grid, dim3(256), 0, s,                     \
-                               reinterpret_cast<const float *>(wave), ld_wave, frame_off, window, tw_fft,          \
-                               tw_unpack, melT, mel_range, nmel, ld_mel, mel, win, shift, scale, preemph,          \
-                               remove_dc, eps);                                                                    \
-        break;
-    switch (log2n) {
-        ASRK_FBANK_CASE(8) ASRK_FBANK_CASE(9) ASRK_FBANK_CASE(10)
-    }
-#undef ASRK_FBANK_CASE
-    asrk_prof_end_(PROF_FBANK, s);
-    ASRK_LAUNCH_CHECK();
-    return ASRK_OK;
+    return fbank_logmel_batch_launch(wave, sample_bytes, ld_wave, n_samples_host, frame_off, B, max_m, window, tw_fft,
+                                     tw_unpack, melT, mel_range, nmel, ld_mel, mel, win, shift, log2n, scale, preemph,
+                                     remove_dc, eps, false, 0.f, nullptr, stream);
+}
+
+extern "C" int asrk_fbank_logmel_batch_dither_f32(const void *wave, int sample_bytes, int64_t ld_wave,
+                                                  const int64_t *n_samples_host, const int64_t *frame_off, int B,
+                                                  int max_m, const float *window, const float *tw_fft,
+                                                  const float *tw_unpack, const float *melT, const int *mel_range,
+                                                  int nmel, int ld_mel, float *mel, int win, int shift, int log2n,
+                                                  float scale, float preemph, int remove_dc, float eps, float dither,
+                                                  const uint64_t *keys, void *stream) {
+    return fbank_logmel_batch_launch(wave, sample_bytes, ld_wave, n_samples_host, frame_off, B, max_m, window, tw_fft,
+                                     tw_unpack, melT, mel_range, nmel, ld_mel, mel, win, shift, log2n, scale, preemph,
+                                     remove_dc, eps, true, dither, keys, stream);
 }
 
 extern "C" int asrk_delta_cmvn_batch_f32(const float *mel, const int64_t *frame_off, int B, int D,

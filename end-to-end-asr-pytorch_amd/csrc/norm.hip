@@ -5,6 +5,7 @@
 // so backward re-derives the same mask from (seed, offset) instead of reading 1 byte/element.
 #include "common.h"
 #include "knobs.h"
+#include "philox.h"
 #include <algorithm>
 
 namespace {
@@ -102,32 +103,6 @@ __global__ __launch_bounds__(256) void ln_bwd_param_kernel(const float *__restri
 }
 
 // ---------------------------------------------------------------- dropout (Philox4x32-10)
-__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3,
-                                             uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-}
-
-__device__ __forceinline__ void philox4x32_10(uint64_t ctr, uint64_t offset, uint64_t seed,
-                                              uint32_t out[4]) {
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32);
-    uint32_t c2 = (uint32_t)offset, c3 = (uint32_t)(offset >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 // y[i] = keep(i) ? x[i] * scale : 0, keep(i) <=> (u32 >> 8) >= thresh24  (thresh24 = round(p*2^24))
 template <bool VEC>
 __global__ __launch_bounds__(256) void dropout_kernel(const float *__restrict__ x,

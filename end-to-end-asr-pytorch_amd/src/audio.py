@@ -132,13 +132,28 @@ class _FbankTables:
         self.fused = 8 <= self.log2n <= 10
 
 
+def _dither_amplitude(value):
+    """the `dither` key as a float; ValueError unless it is a finite, non-negative number"""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value < 0:
+        raise ValueError('dither must be a finite, non-negative number (in units of the [-1, 1) waveform), got %r'
+                         % (value,))
+    return float(value)
+
+
+def _keys_to_device(keys, device):
+    """64-bit dither keys -> the device array the batch entries read (uint64 bits carried in an int64 tensor)"""
+    k = np.asarray([int(v) & _M64 for v in keys], dtype=np.uint64)
+    return torch.from_numpy(k.view(np.int64)).to(device)
+
+
 def kaldi_fbank(waveform, sample_frequency, num_mel_bins=23, frame_length=25.0, frame_shift=10.0,
                 dither=0.0, channel=-1, preemphasis_coefficient=0.97, remove_dc_offset=True,
-                low_freq=20.0, high_freq=0.0, **unused):
+                low_freq=20.0, high_freq=0.0, dither_key=0, **unused):
     """torchaudio.compliance.kaldi.fbank restated for the device (subset used at audio.py:104-108):
-    waveform [C, N] on the GPU -> log-mel energies [m, num_mel_bins]."""
-    if dither != 0.0:
-        raise NotImplementedError('dither > 0 is random; the shipped configs set dither: 0')
+    waveform [C, N] on the GPU -> log-mel energies [m, num_mel_bins].  dither > 0 adds dither * z(dither_key, frame,
+    position) to every frame element (the noise function of include/asrk.h: a pure function of the 64-bit key, where
+    torchaudio draws from the global generator); dither == 0 makes the plain calls and ignores the key."""
+    dither = _dither_amplitude(dither)
     if unused:
         raise NotImplementedError('unsupported fbank options: %s' % sorted(unused))
     ops._require_gpu(waveform)
@@ -152,26 +167,35 @@ def kaldi_fbank(waveform, sample_frequency, num_mel_bins=23, frame_length=25.0, 
     if m == 0:
         return torch.empty((0, num_mel_bins), dtype=torch.float32, device=dev)
     if tb.fused:
+        keys = _keys_to_device([dither_key], dev) if dither > 0.0 else None
         return _pcm_to_logmel(x, 4, n, None, torch.tensor([0, m], dtype=torch.int64, device=dev), 1, m, m, tb,
-                              num_mel_bins, 1.0, preemphasis_coefficient, remove_dc_offset)
+                              num_mel_bins, 1.0, preemphasis_coefficient, remove_dc_offset, dither, keys)
     frames = torch.empty((m, tb.ldf), dtype=torch.float32, device=dev)
-    _lib.check(L.asrk_fbank_frames_f32(_p(x), n, _p(tb.window), _p(frames), m, tb.win, tb.shift, tb.ldf,
-                                       preemphasis_coefficient, int(remove_dc_offset), _stream()),
-               'fbank_frames')
+    if dither > 0.0:
+        _lib.check(L.asrk_fbank_frames_dither_f32(_p(x), n, _p(tb.window), _p(frames), m, tb.win, tb.shift, tb.ldf,
+                                                  preemphasis_coefficient, int(remove_dc_offset), dither,
+                                                  int(dither_key) & _M64, _stream()), 'fbank_frames_dither')
+    else:
+        _lib.check(L.asrk_fbank_frames_f32(_p(x), n, _p(tb.window), _p(frames), m, tb.win, tb.shift, tb.ldf,
+                                           preemphasis_coefficient, int(remove_dc_offset), _stream()),
+                   'fbank_frames')
     return _frames_to_logmel(frames, tb, num_mel_bins)
 
 
 def _pcm_to_logmel(wave, sample_bytes, ld_wave, n_host, frame_off, B, max_m, rows, tb, num_mel_bins, scale, preemph,
-                   remove_dc):
+                   remove_dc, dither=0.0, keys=None):
     """padded PCM batch [B, ld_wave] -> log-mel energies [sum m, num_mel_bins] in ONE launch (csrc/audio.hip
-    fbank_logmel_batch_kernel: framing, FFT in LDS, power, mel weights, log) - no frames / spectrum / power tensors"""
+    fbank_logmel_batch_kernel: framing, FFT in LDS, power, mel weights, log) - no frames / spectrum / power tensors.
+    dither > 0: the dithered entry with keys [B] (device); dither == 0: the plain entry, keys are not looked at"""
     mel = torch.empty((rows, num_mel_bins), dtype=torch.float32, device=wave.device)
-    _lib.check(_L().asrk_fbank_logmel_batch_f32(_p(wave), sample_bytes, ld_wave,
-                                                n_host.ctypes.data if n_host is not None else None, _p(frame_off), B,
-                                                max_m, _p(tb.window), _p(tb.tw_fft), _p(tb.tw_unpack), _p(tb.melT),
-                                                _p(tb.mel_range), num_mel_bins, num_mel_bins, _p(mel), tb.win, tb.shift,
-                                                tb.log2n, float(scale), float(preemph), int(remove_dc), FLT_EPS,
-                                                _stream()), 'fbank_logmel_batch')
+    args = (_p(wave), sample_bytes, ld_wave, n_host.ctypes.data if n_host is not None else None, _p(frame_off), B,
+            max_m, _p(tb.window), _p(tb.tw_fft), _p(tb.tw_unpack), _p(tb.melT), _p(tb.mel_range), num_mel_bins,
+            num_mel_bins, _p(mel), tb.win, tb.shift, tb.log2n, float(scale), float(preemph), int(remove_dc), FLT_EPS)
+    if dither > 0.0:
+        _lib.check(_L().asrk_fbank_logmel_batch_dither_f32(*args, float(dither), _p(keys), _stream()),
+                   'fbank_logmel_batch_dither')
+    else:
+        _lib.check(_L().asrk_fbank_logmel_batch_f32(*args, _stream()), 'fbank_logmel_batch')
     return mel
 
 
@@ -323,16 +347,22 @@ class ExtractAudioFeature(nn.Module):
         self.device = device
 
     def forward(self, filepath):
-        ''' filepath: a path, (waveform, sample_rate), or (waveform, sample_rate, speed): channel 0 of the waveform is
-            then speed-perturbed on the device first (the kernel of the whole-batch form, B = 1) '''
-        speed = None
+        ''' filepath: a path, (waveform, sample_rate), (waveform, sample_rate, speed) or (waveform, sample_rate, speed,
+            dither_key).  With a speed (None: none) channel 0 of the waveform is speed-perturbed on the device first (the
+            kernel of the whole-batch form, B = 1).  The key matters only under dither > 0; without one a path gets the
+            evaluation key of seed 0 for its file name (Dither(.., 0).key(name, False)) and a tensor key 0. '''
+        speed, key = None, None
         if isinstance(filepath, (tuple, list)):
-            if len(filepath) == 3:
+            if len(filepath) == 4:
+                waveform, sample_rate, speed, key = filepath
+            elif len(filepath) == 3:
                 waveform, sample_rate, speed = filepath
             else:
                 waveform, sample_rate = filepath
         else:
             waveform, sample_rate = load_wav(filepath)
+            if self.kwargs.get('dither', 0.0) != 0.0:
+                key = Dither(self.kwargs['dither'], 0).key(utt_name(filepath), False)
         waveform = waveform.to(self.device)
         if speed is not None and float(speed) != 1.0:
             x = _f32c(waveform[0]).reshape(1, -1)
@@ -340,7 +370,7 @@ class ExtractAudioFeature(nn.Module):
             waveform = y[:, :int(n_out[0])]
         extract = kaldi_fbank if self.mode == "fbank" else kaldi_mfcc
         y = extract(waveform, num_mel_bins=self.num_mel_bins, channel=-1,
-                    sample_frequency=sample_rate, **self.kwargs)
+                    sample_frequency=sample_rate, dither_key=0 if key is None else key, **self.kwargs)
         return _transpose2d(y).unsqueeze(0).detach()
 
     def frame_shift_ms(self):
@@ -396,7 +426,8 @@ class BatchFeatureTransform:
     (framing, FFT in LDS, power, mel weights, log; FFT sizes 256, 512, 1024) -> delta + CMVN + layout + zero padding in
     one kernel -> (feat [B, Tmax, (order+1)*D], feat_len [B]).  FFT sizes outside 256..1024 take the unfused route
     instead of the first launch: batched framing kernel -> DFT GEMM -> power -> mel GEMM -> log; mfcc adds one DCT
-    GEMM; speed factors one resampling launch in front.  Same arithmetic per frame as the per-file modules (the
+    GEMM; speed factors one resampling launch in front; `dither` > 0 takes the dithered entry of the first launch (one
+    64-bit key per utterance, no further launch).  Same arithmetic per frame as the per-file modules (the
     framing is the same code; CMVN sums in a different order: agreement ~1e-6).  Delta filters of up to 15 taps
     (17 and more raise NotImplementedError; create_transform then serves the per-file chain alone)."""
 
@@ -415,8 +446,7 @@ class BatchFeatureTransform:
         self.remove_dc = cfg.pop("remove_dc_offset", True)
         self.low_freq, self.high_freq = cfg.pop("low_freq", 20.0), cfg.pop("high_freq", 0.0)
         self.num_ceps, self.lifter = cfg.pop("num_ceps", 13), cfg.pop("cepstral_lifter", 22.0)
-        if cfg.pop("dither", 0.0) != 0.0:
-            raise NotImplementedError('dither > 0 is random; the shipped configs set dither: 0')
+        self.dither = _dither_amplitude(cfg.pop("dither", 0.0))
         cfg.pop("channel", None)
         if cfg:
             raise NotImplementedError('unsupported fbank options: %s' % sorted(cfg))
@@ -432,14 +462,20 @@ class BatchFeatureTransform:
         win, shift = int(sample_rate * self.frame_length * 0.001), int(sample_rate * self.frame_shift * 0.001)
         return 0 if n_samples < win else 1 + (n_samples - win) // shift
 
-    def __call__(self, waves, sample_rate, speeds=None):
+    def __call__(self, waves, sample_rate, speeds=None, dither_keys=None):
         """waves: list of 1-D int16 numpy arrays (raw PCM; uploaded as 2-byte samples) or float32 arrays /
         tensors in [-1, 1) -> (feat [B, Tmax, out_dim] on the device, zero padded, feat_len LongTensor [B]).
         speeds: one speed-perturbation factor per utterance (SpeedPerturb), or None.  Utterance b is resampled on the
         device by speeds[b] before the filterbank (one more launch: ops.resample_rows) and feat_len counts the frames
-        of the PERTURBED waveform; None, or all factors 1.0, is the plain path: no extra launch, the same bits."""
+        of the PERTURBED waveform; None, or all factors 1.0, is the plain path: no extra launch, the same bits.
+        dither_keys: one 64-bit key per utterance (Dither.key), required when the config's dither is > 0: the noise
+        of utterance b is a pure function of dither_keys[b] and acts on the perturbed waveform; with dither 0 they are
+        ignored and the launches are the plain ones."""
         L = _L()
         dev, B = self.device, len(waves)
+        if self.dither > 0.0 and (dither_keys is None or len(dither_keys) != B):
+            raise ValueError('dither = %g needs one key per utterance: got %s for %d utterances'
+                             % (self.dither, 'none' if dither_keys is None else len(dither_keys), B))
         is_i16 = all(isinstance(w, np.ndarray) and w.dtype == np.int16 for w in waves)
         arrs = [w if is_i16 else torch.as_tensor(w, dtype=torch.float32).reshape(-1).numpy() for w in waves]
         ns_src = [int(a.shape[0]) for a in arrs]
@@ -496,21 +532,19 @@ class BatchFeatureTransform:
         offs[1:] = np.cumsum(ms)
         frame_off = torch.from_numpy(offs).to(dev)
         n_host = np.asarray(ns, dtype=np.int64)
+        keys = _keys_to_device(dither_keys, dev) if self.dither > 0.0 else None
         if tb.fused:
-            mel = torch.empty((total, self.feat_dim), dtype=torch.float32, device=dev)
-            _lib.check(L.asrk_fbank_logmel_batch_f32(_p(wave), sbytes, nmax, n_host.ctypes.data,
-                                                     _p(frame_off), B, Tmax, _p(tb.window), _p(tb.tw_fft),
-                                                     _p(tb.tw_unpack), _p(tb.melT), _p(tb.mel_range), self.feat_dim,
-                                                     self.feat_dim, _p(mel), tb.win, tb.shift, tb.log2n,
-                                                     scale, self.preemph,
-                                                     int(self.remove_dc), FLT_EPS, _stream()), 'fbank_logmel_batch')
+            mel = _pcm_to_logmel(wave, sbytes, nmax, n_host, frame_off, B, Tmax, total, tb, self.feat_dim, scale,
+                                 self.preemph, self.remove_dc, self.dither, keys)
         else:
             frames = torch.empty((total, tb.ldf), dtype=torch.float32, device=dev)
-            _lib.check(L.asrk_fbank_frames_batch_f32(_p(wave), sbytes, nmax,
-                                                     n_host.ctypes.data, _p(frame_off), B, Tmax, _p(tb.window),
-                                                     _p(frames), tb.win, tb.shift, tb.ldf,
-                                                     scale, self.preemph,
-                                                     int(self.remove_dc), _stream()), 'fbank_frames_batch')
+            args = (_p(wave), sbytes, nmax, n_host.ctypes.data, _p(frame_off), B, Tmax, _p(tb.window), _p(frames),
+                    tb.win, tb.shift, tb.ldf, scale, self.preemph, int(self.remove_dc))
+            if self.dither > 0.0:
+                _lib.check(L.asrk_fbank_frames_batch_dither_f32(*args, self.dither, _p(keys), _stream()),
+                           'fbank_frames_batch_dither')
+            else:
+                _lib.check(L.asrk_fbank_frames_batch_f32(*args, _stream()), 'fbank_frames_batch')
             mel = _frames_to_logmel(frames, tb, self.feat_dim)
         if self.feat_type == "mfcc":
             tab = _mfcc_table(self.feat_dim, self.num_ceps, self.lifter, dev)
@@ -732,6 +766,52 @@ class SpeedPerturb:
     def create_msg(self):
         return 'SpeedPerturb| factors = {} (orig:new = {}) | drawn per utterance and epoch, the same on every rank' \
             .format(self.factors, ', '.join('%d:%d' % r for r in self.ratios))
+
+
+def utt_name(path):
+    """file name without directories and extensions: the name the stateless draws hash"""
+    return str(path).split('/')[-1].split('.')[0]
+
+
+class Dither:
+    """Key policy of the dithered filterbank (the reference's `data.audio.dither`, forwarded to torchaudio's kaldi
+    fbank / mfcc, which add randn * dither to every frame).  The amplitude is in the units of the [-1, 1) waveform:
+    Kaldi's default of 1.0 belongs to the int16 scale and is 1 / 32768 = 3.05e-5 here.
+
+    The device draws the noise of an utterance as a pure function of one 64-bit key (include/asrk.h); this class deals
+    the keys, stateless and the same on every data-parallel rank: a function of (seed, epoch_key, utterance name) for
+    training - `begin_epoch(key)` as for SpeedPerturb - and of (seed, utterance name) alone for evaluation, so dev and
+    test features are the same on every pass, rank and run (the reference redraws them: DESIGN.md section 1,
+    deviation viii)."""
+
+    TAG = 0x6474685F6B657931         # keeps the stream apart from SpeedPerturb.factor's hash of the same triple
+
+    def __init__(self, amplitude, seed=0):
+        self.amplitude = _dither_amplitude(amplitude)
+        self.seed, self.epoch_key = int(seed), 0
+
+    @classmethod
+    def from_config(cls, cfg, seed=0):
+        """cfg: the whole yaml config (a mapping) -> a policy for cfg['data']['audio']['dither'], None when the key is
+        absent or 0; ValueError for a negative, non-finite or non-numeric value"""
+        block = cfg.get('data') if cfg is not None else None
+        block = block.get('audio') if isinstance(block, dict) else None
+        if not isinstance(block, dict) or 'dither' not in block:
+            return None
+        policy = cls(block['dither'], seed)
+        return policy if policy.amplitude > 0.0 else None
+
+    def begin_epoch(self, epoch_key):
+        self.epoch_key = int(epoch_key)
+
+    def key(self, name, train):
+        """the 64-bit key of utterance `name`: of the current epoch when train, of epoch key 0 otherwise"""
+        ek = self.epoch_key if train else 0
+        return _splitmix64((self.seed & _M64) ^ _splitmix64(ek & _M64) ^ zlib.crc32(name.encode()) ^ self.TAG)
+
+    def create_msg(self):
+        return 'Dither     | amplitude = {:g} of the [-1, 1) waveform ({:g} on the int16 scale) | per (frame, position), ' \
+               'keyed by utterance and epoch; fixed for dev / test'.format(self.amplitude, self.amplitude * 32768.0)
 
 
 def create_transform(audio_config, device='cuda'):

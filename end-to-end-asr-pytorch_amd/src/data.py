@@ -20,7 +20,7 @@ from torch.nn.utils.rnn import pad_sequence
 from .text import load_text_encoder
 import os
 
-from .audio import create_transform, load_wav, load_pcm, audio_num_samples
+from .audio import create_transform, load_wav, load_pcm, audio_num_samples, Dither
 
 # Batch size will be halved if the longest wavefile surpasses threshold (reference: src/data.py:8-11)
 HALF_BATCHSIZE_AUDIO_LEN = 800
@@ -83,11 +83,11 @@ def _utt_name(path):
 
 
 class _Speeds:
-    ''' what the collate function asks of a SpeedPerturb policy (src/audio.py), or of none: the factor of a file, its
-        sample count after perturbation, and the per-file chain's input for it '''
+    ''' what the collate function asks of a SpeedPerturb policy and a Dither policy (src/audio.py), or of none: the
+        factor of a file, its sample count after perturbation, its dither key, and the per-file chain's input for it '''
 
-    def __init__(self, policy):
-        self.policy = policy
+    def __init__(self, policy, dither=None, train=False):
+        self.policy, self.dither, self.train = policy, dither, train
 
     def factor(self, path):
         return self.policy.factor(_utt_name(path))
@@ -95,25 +95,41 @@ class _Speeds:
     def samples(self, n, path):
         return n if self.policy is None else self.policy.out_samples(n, self.factor(path))
 
+    def key(self, path):
+        return self.dither.key(_utt_name(path), self.train)
+
+    def keys(self, paths):
+        ''' BatchFeatureTransform's dither_keys for these files: None without a Dither policy '''
+        return None if self.dither is None else [self.key(p) for p in paths]
+
+    def plain(self):
+        return self.policy is None and self.dither is None
+
     def wav(self, path):
         ''' load_wav's (waveform, sample_rate), with the file's factor appended under a policy (ExtractAudioFeature
-            then resamples on the device: the per-file chain never drops the augmentation) '''
+            then resamples on the device: the per-file chain never drops the augmentation), and its dither key behind
+            that under a Dither policy (the factor is then None without a speed policy) '''
+        if self.dither is not None:
+            return load_wav(path) + (None if self.policy is None else self.factor(path), self.key(path))
         return load_wav(path) if self.policy is None else load_wav(path) + (self.factor(path),)
 
 
-def collect_audio_batch(batch, audio_transform, mode, n_jobs=1, shard=None, speed_perturb=None):
+def collect_audio_batch(batch, audio_transform, mode, n_jobs=1, shard=None, speed_perturb=None, dither=None,
+                        train=False):
     ''' [(audio_path, [token ids]), ...] (or one bucket of them) ->
         (names, feat [B,T,D] on the transform's device, feat_len [B], text [B,L])
         (reference: src/data.py:14-46).  shard = (rank, world): `batch` is the GLOBAL batch of a data-parallel step;
         the halving rule is applied to it as a whole, then this rank keeps its length-balanced share (§8e cond. 5).
         speed_perturb: a SpeedPerturb policy (src/audio.py) or None; under a policy every length that decides something
-        here - halving, dealing, the order within the batch, feat_len - is the PERTURBED one. '''
+        here - halving, dealing, the order within the batch, feat_len - is the PERTURBED one.
+        dither: a Dither policy (src/audio.py) or None; every file's key is dither.key(name, train) on the whole-batch
+        path and on the per-file fallback alike (train: the training loader's epoch-keyed draw). '''
     if type(batch[0]) is not tuple:
         batch = batch[0]
     paths = [str(b[0]) for b in batch]
     pool = _pool(n_jobs)
     bt = getattr(audio_transform, 'batch', None)
-    sp = _Speeds(speed_perturb)
+    sp = _Speeds(speed_perturb, dither, train)
     if bt is not None and os.environ.get('ASRK_BATCH_FBANK', '1') != '0':
         try:
             return _collect_audio_batch_device(batch, paths, bt, mode, pool, shard, sp)
@@ -121,7 +137,7 @@ def collect_audio_batch(batch, audio_transform, mode, n_jobs=1, shard=None, spee
             pass
     with torch.no_grad():
         # the first utterance of a bucket is the longest transcript: its frame count decides halving
-        first = audio_transform(paths[0] if speed_perturb is None else sp.wav(paths[0]))
+        first = audio_transform(paths[0] if sp.plain() else sp.wav(paths[0]))
         if first.shape[0] > HALF_BATCHSIZE_AUDIO_LEN and mode == 'train':
             batch, paths = batch[:_half(len(batch), shard)], paths[:_half(len(batch), shard)]
         if shard is not None and shard[1] > 1:
@@ -182,7 +198,8 @@ def _collect_audio_batch_device(batch, paths, bt, mode, pool, shard=None, sp=_Sp
         read raw 16-bit PCM, ONE padded int16 upload, 7 launches for the batch.  Frame counts follow from the
         sample counts (snip-edges framing), so the halving rule (src/data.py:22-24) and the descending-length
         order (src/data.py:36-37) are decided before anything is extracted - no file is processed twice.  Under a
-        speed-perturbation policy (sp) the sample counts are the perturbed ones and the resampling is one more launch. '''
+        speed-perturbation policy (sp) the sample counts are the perturbed ones and the resampling is one more launch;
+        under a Dither policy every utterance's key goes with it (no further launch). '''
     n0, sr = _num_samples_or_defer(paths[0])
     if bt.frame_count(sp.samples(n0, paths[0]), sr) > HALF_BATCHSIZE_AUDIO_LEN and mode == 'train':
         batch, paths = batch[:_half(len(batch), shard)], paths[:_half(len(batch), shard)]
@@ -200,10 +217,14 @@ def _collect_audio_batch_device(batch, paths, bt, mode, pool, shard=None, sp=_Sp
     # descending audio length within the batch; sorted() is stable, so ties keep their order
     order = sorted(range(len(pcm)), key=lambda i: frames[i], reverse=True)
     with torch.no_grad():
-        if sp.policy is None:
+        if sp.plain():
             audio_feat, audio_len = bt([pcm[i] for i in order], sr)
-        else:
+        elif sp.dither is None:
             audio_feat, audio_len = bt([pcm[i] for i in order], sr, speeds=[sp.factor(paths[i]) for i in order])
+        else:
+            speeds = None if sp.policy is None else [sp.factor(paths[i]) for i in order]
+            audio_feat, audio_len = bt([pcm[i] for i in order], sr, speeds=speeds,
+                                       dither_keys=sp.keys([paths[i] for i in order]))
     names = tuple(_utt_name(paths[i]) for i in order)
     text = pad_sequence([torch.LongTensor(batch[i][1]) for i in order], batch_first=True)
     return names, audio_feat, audio_len, text
@@ -289,13 +310,21 @@ def load_textset(n_jobs, use_gpu, pin_memory, corpus, text):
     return tr_set, dv_set, tokenizer.vocab_size, tokenizer, data_msg
 
 
-def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, speed_perturb=None):
+def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, speed_perturb=None, dither=None):
     ''' (reference: src/data.py:128-157) -> (tr_loader, dv_loader, feat_dim, vocab_size, tokenizer, msg).
         `use_gpu` must be true (there is no CPU feature path); `pin_memory` is accepted and unused.
         speed_perturb: a SpeedPerturb policy (src/audio.py) for the TRAINING loader's collate function, or None; the
-        dev / test loaders never perturb. '''
+        dev / test loaders never perturb.
+        dither: a Dither policy (src/audio.py) when audio['dither'] > 0, else None: it deals the keys of every loader;
+        only the loader of a training split draws them per epoch, dev / test keys depend on (seed, name) alone.  A
+        config with dither > 0 and no policy - the decoding solver, which passes none - gets the policy of the seed
+        torch's global generator was seeded with: main.py seeds it with --seed before any solver is built (the same
+        number _dp_sampler relies on), so decoding under the training run's --seed extracts the dev features that
+        run validated on. '''
     if not use_gpu:
         raise RuntimeError("the feature pipeline runs in gfx950 kernels; --cpu is not supported")
+    if dither is None and audio.get('dither', 0):
+        dither = Dither(audio['dither'], int(torch.initial_seed()) & 0x7fffffffffffffff)
     audio_transform, feat_dim = create_transform(audio.copy(), device='cuda')
     tokenizer = load_text_encoder(**text)
     rank, world = _dp_world()
@@ -310,8 +339,10 @@ def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, sp
         # the global batch) and keeps its length-balanced share of each (deal_global_batch)
         sampler, shard = _dp_sampler(len(tr_set), tr_loader_bs, world, shuffle), (rank, world)
     collect_tr = partial(collect_audio_batch, audio_transform=audio_transform, mode=mode, n_jobs=n_jobs, shard=shard,
-                         speed_perturb=speed_perturb if mode == 'train' else None)
-    collect_dv = partial(collect_audio_batch, audio_transform=audio_transform, mode='test', n_jobs=n_jobs)
+                         speed_perturb=speed_perturb if mode == 'train' else None, dither=dither,
+                         train=mode == 'train')
+    collect_dv = partial(collect_audio_batch, audio_transform=audio_transform, mode='test', n_jobs=n_jobs,
+                         dither=dither)
     tr_set = DataLoader(tr_set, batch_size=tr_loader_bs, shuffle=shuffle and sampler is None,
                         sampler=sampler, drop_last=shuffle,
                         collate_fn=collect_tr, num_workers=0)

@@ -872,6 +872,37 @@ int asrk_fbank_logmel_batch_f32(const void *wave, int sample_bytes, int64_t ld_w
                                 float *mel, int win, int shift, int log2n, float scale, float preemph, int remove_dc,
                                 float eps, void *stream);
 
+/* ---- Dither (the reference's `audio.dither` key, forwarded to torchaudio.compliance.kaldi.fbank / mfcc, whose
+ * _get_window adds randn(strided_input.shape) * dither to the strided frame matrix BEFORE DC removal) ------------------
+ * The three framing entries above, with x replaced by
+ *     v[f][j] = x[f*shift + j] + dither * z(key, f, j),        f = frame within the utterance, j = 0..win-1,
+ * x the sample after `scale`; product and sum are two f32 operations (not fused).  Everything behind is the plain
+ * entry's arithmetic on v: mean over the frame, pre-emphasis with the replicated v[f][0], window, ...  The noise is per
+ * (frame, position), not per waveform sample: two overlapping frames see different noise on one sample.  `dither` is in
+ * the units of the [-1, 1) waveform: 1/32768 = 3.05e-5 is Kaldi's int16-scale default of 1.0.
+ * z is a pure function, the same in every batch composition, launch and run:
+ *     (r0, r1, r2, r3) = Philox4x32-10(counter words (j >> 2, f, 0, 0), key words (key & 0xffffffff, key >> 32))
+ *     u1 = ((r0 >> 8) + 1) * 2^-24,  u2 = (r1 >> 8) * 2^-24      (u1 in (0, 1], u2 in [0, 1), exact in f32)
+ *     z0 = sqrt(-2 ln u1) * cos(2 pi u2),  z1 = sqrt(-2 ln u1) * sin(2 pi u2);   z2, z3 likewise from r2, r3
+ *     z(key, f, j) = z[j & 3];   |z| <= sqrt(48 ln 2) = 5.77
+ * evaluated in f32 with the accurate logf / sqrtf / sincospif (tests/dither_reference.py restates it in float64).
+ * key: one per utterance; the per-file entry takes it by value, the batch entries as keys [B] (uint64, DEVICE).
+ * Arguments, results and refusals are the plain entries'; in addition ASRK_EINVAL for a negative or non-finite dither
+ * (checked with the sizes) and for keys == NULL (checked with the other pointers).  dither = 0 is taken: v = x. */
+int asrk_fbank_frames_dither_f32(const float *wave, int64_t n_samples, const float *window, float *frames, int m,
+                                 int win, int shift, int ldf, float preemph, int remove_dc, float dither, uint64_t key,
+                                 void *stream);
+int asrk_fbank_frames_batch_dither_f32(const void *wave, int sample_bytes, int64_t ld_wave,
+                                       const int64_t *n_samples_host, const int64_t *frame_off, int B, int max_m,
+                                       const float *window, float *frames, int win, int shift, int ldf, float scale,
+                                       float preemph, int remove_dc, float dither, const uint64_t *keys, void *stream);
+int asrk_fbank_logmel_batch_dither_f32(const void *wave, int sample_bytes, int64_t ld_wave,
+                                       const int64_t *n_samples_host, const int64_t *frame_off, int B, int max_m,
+                                       const float *window, const float *tw_fft, const float *tw_unpack,
+                                       const float *melT, const int *mel_range, int nmel, int ld_mel, float *mel,
+                                       int win, int shift, int log2n, float scale, float preemph, int remove_dc,
+                                       float eps, float dither, const uint64_t *keys, void *stream);
+
 /* ---- SpecAugment on the padded feature batch (training input augmentation; the reference keeps the SpecAugment
  * learning-rate schedules, src/optim.py:65-82, and augments nothing: the call sits between fetch_data and the model
  * call of bin/train_asr.py:99-105) -----------------------------------------------------------------------------------
