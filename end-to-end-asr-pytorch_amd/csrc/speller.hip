@@ -1814,6 +1814,30 @@ extern "C" int asrk_speller_plan_info(const asrk_speller_t *d, int *info) {
     return ASRK_OK;
 }
 
+// F2b, which softmax/context kernel a step launches: the row-grouped kernel where the caller promised groups
+// (row_group = RG > 1, every group whole, one head, no shared memory), its weights fit 64 KiB of LDS and the grid of
+// groups still fills the chip (a few groups: the per-row grid fills it better); else the per-row kernel, with 16-byte
+// loads where Dv and the pointers allow.  ctxh_t = where the step's per-head contexts go.
+enum { CTX_SCALAR = 0, CTX_VECTOR = 1, CTX_GROUP = 2 };
+static int ctx_variant(const asrk_speller_t &d, const float *ctxh_t) {
+    const bool vec = al16(d.value) && d.Dv % 4 == 0;
+    const int RG = d.row_group;
+    const size_t lds_g = (size_t)RG * ((d.Te + 3) & ~3) * sizeof(float);
+    if (RG > 1 && RG <= 8 * CG_MAXR && n_heads(d) == 1 && vec && d.B % RG == 0 && al16(ctxh_t) && d.Dv % 4 == 0 &&
+        lds_g <= 64 * 1024 && !d.shared_kv && (d.B / RG) * asrk_div_up(d.Dv, 256) >= 64)
+        return CTX_GROUP;
+    return vec ? CTX_VECTOR : CTX_SCALAR;
+}
+
+extern "C" int asrk_speller_ctx_variant(const asrk_speller_t *d, int *variant) {
+    if (!variant) return ASRK_EINVAL;
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (d->row_group < 0) return ASRK_EINVAL;
+    *variant = ctx_variant(*d, n_heads(*d) > 1 ? d->ctxh : d->ctx);   // slot 0; a null pointer counts as aligned
+    return ASRK_OK;
+}
+
 // One attention + decoder-cell step (also the body of the training loop).  `step` selects the tape
 // slots; prev = previous attention row pointer + row stride.
 static int speller_step_fwd(const asrk_speller_t &d, const Plan &pl, int t, const float *prev, long prev_ld,
@@ -1851,14 +1875,13 @@ static int speller_step_fwd(const asrk_speller_t &d, const Plan &pl, int t, cons
     {   // F2b
         CtxArgs a{d.e_scratch, d.value, attn_t, ctxh_t, d.attn_ld, (long)Dv, Te, Dv, d.shared_kv ? 0 : 1, d.row_mem};
         a.stamps = sp_slot(t, 2);
-        const bool vec = al16(d.value) && Dv % 4 == 0;
         const dim3 grid(BN, asrk_div_up(Dv, 256));
         const int RG = d.row_group;
         const size_t lds_g = (size_t)RG * ((Te + 3) & ~3) * sizeof(float);
-        if (RG > 1 && RG <= 8 * CG_MAXR && NH == 1 && vec && B % RG == 0 && al16(ctxh_t) && Dv % 4 == 0 &&
-            lds_g <= 64 * 1024 && !d.shared_kv && (B / RG) * asrk_div_up(Dv, 256) >= 64)   // a few groups: the per-row grid fills the chip better
+        const int variant = ctx_variant(d, ctxh_t);
+        if (variant == CTX_GROUP)
             hipLaunchKernelGGL(softmax_context_group_kernel, dim3(B / RG, asrk_div_up(Dv, 256)), dim3(512), lds_g, s, a, RG);
-        else if (vec) hipLaunchKernelGGL(softmax_context_kernel<true>, grid, dim3(512), pl.lds_ctx, s, a);
+        else if (variant == CTX_VECTOR) hipLaunchKernelGGL(softmax_context_kernel<true>, grid, dim3(512), pl.lds_ctx, s, a);
         else hipLaunchKernelGGL(softmax_context_kernel<false>, grid, dim3(512), pl.lds_ctx, s, a);
     }
     if (NH > 1) {   // merge_head (src/asr.py:308-311): ctx [B,Dv] = [ctx_head_0 | ... ] Wm^T + bm

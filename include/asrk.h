@@ -606,6 +606,12 @@ int asrk_speller_plan(const asrk_speller_t *dims, int *tc_fwd, int *tc_bwd);
  * workgroup; KP = padded row pitch of Wp in LDS; ctx_vec = Dv % 4 == 0 (vector softmax/context kernel, given a
  * 16-byte aligned value).  Dot-product plans (att_mode 1) report 0 in the first four slots. */
 int asrk_speller_plan_info(const asrk_speller_t *dims, int *info);
+/* read-only report of the softmax/context kernel a step of this descriptor launches for slot 0, from the function the
+ * launch itself calls (host only, nothing is launched): *variant = 0 per-row kernel with scalar loads, 1 per-row kernel
+ * with 16-byte loads (Dv % 4 == 0, aligned value), 2 the row-grouped kernel (row_group = RG in 2..32, B % RG == 0, one
+ * head, no shared_kv, RG * round4(Te) floats <= 64 KiB, (B / RG) * ceil(Dv / 256) >= 64 workgroups).  Alignment is read
+ * from the descriptor's value / ctx pointers; a null pointer counts as aligned. */
+int asrk_speller_ctx_variant(const asrk_speller_t *dims, int *variant);
 int asrk_speller_fwd_f32(const asrk_speller_t *p, void *stream);
 int asrk_speller_bwd_f32(const asrk_speller_t *p, const asrk_speller_bwd_t *g, void *stream);
 /* one attention + decoder-cell step outside the training loop (greedy / beam decoding,

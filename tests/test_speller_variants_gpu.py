@@ -4,10 +4,7 @@ tests/speller_reference.py, on the case table kept there: one small shape or mor
 kernel, per softmax/context kernel and per boundary between two of them (tests/test_speller_plan_cpu.py holds every
 shape to its variant).  Outputs and the gradient of every input and weight; tolerances are those of
 tests/test_cfg3_gpu.py: 1e-3 relative on outputs, 2e-3 on gradients, gen_energy.bias (exactly 0 by the shift
-invariance of softmax) absolute on both sides.
-
-Not covered here: the row-grouped softmax/context kernel (asrk_speller_t::row_group > 1), which only
-MultiSpellerStepper's decode path launches."""
+invariance of softmax) absolute on both sides."""
 import importlib
 
 import pytest
