@@ -86,6 +86,9 @@ SIGNATURES = {
                                       c_vp]),
     "asrk_resample_rows_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_i64,
                                        c_f32, c_vp]),
+    "asrk_reverb_mix_ws_bytes": (c_sz, [c_int, c_i64]),
+    "asrk_reverb_mix_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
+                                    c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_f32, c_vp, c_sz, c_vp]),
     "asrk_lstm_ws_bytes": (c_sz, []),
     "asrk_lstm_xchg_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "asrk_lstm_plan_workgroups": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),

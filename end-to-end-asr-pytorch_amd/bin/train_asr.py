@@ -13,7 +13,7 @@ from ..src.solver import BaseSolver
 from ..src.asr import ASR
 from ..src.optim import Optimizer
 from ..src.data import load_dataset
-from ..src.audio import SpecAugment, SpeedPerturb, Dither
+from ..src.audio import SpecAugment, SpeedPerturb, Dither, NoiseReverb
 from ..src.loss import LossOptions
 from ..src.util import human_format, cal_er
 
@@ -48,14 +48,20 @@ class Solver(BaseSolver):
         # the filterbank's dither (data.audio.dither; None = 0 or absent: no launch changes): one key per utterance,
         # per epoch for the training loader, fixed for the dev loader
         self.dither = Dither.from_config(self.config, seed=self.paras.seed)
+        # reverberation and additive noise of the training loader (top-level `noise_reverb:` block; None = no launch
+        # changes); drawn per (seed, epoch, utterance name) like the speed factors; never applied to the dev loader
+        self.noise_reverb = NoiseReverb.from_config(self.config, seed=self.paras.seed)
         self.tr_set, self.dv_set, self.feat_dim, self.vocab_size, self.tokenizer, msg = \
             load_dataset(self.paras.njobs, self.paras.gpu, self.paras.pin_memory,
-                         self.curriculum > 0, speed_perturb=self.speed, dither=self.dither, **self.config['data'])
+                         self.curriculum > 0, speed_perturb=self.speed, dither=self.dither,
+                         noise_reverb=self.noise_reverb, **self.config['data'])
         self.verbose(msg)
         if self.speed is not None:
             self.verbose(self.speed.create_msg())
         if self.dither is not None:
             self.verbose(self.dither.create_msg())
+        if self.noise_reverb is not None:
+            self.verbose(self.noise_reverb.create_msg())
         # training-time input augmentation (top-level `specaug:` block; None = the step is exactly what it was)
         audio = self.config['data']['audio']
         self.specaug = SpecAugment.from_config(self.config, audio['feat_dim'], audio.get('delta_order', 0) + 1)
@@ -141,7 +147,8 @@ class Solver(BaseSolver):
                 self.verbose('Curriculum learning ends after {} epochs, starting random sampling.'.format(n_epochs))
                 self.tr_set, _, _, _, _, _ = load_dataset(self.paras.njobs, self.paras.gpu,
                                                           self.paras.pin_memory, False, speed_perturb=self.speed,
-                                                          dither=self.dither, **self.config['data'])
+                                                          dither=self.dither, noise_reverb=self.noise_reverb,
+                                                          **self.config['data'])
             if hasattr(self.tr_set.sampler, 'set_epoch'):     # data parallel: the shared shuffle of this epoch
                 self.tr_set.sampler.set_epoch(n_epochs)
             if self.speed is not None:
@@ -150,6 +157,8 @@ class Solver(BaseSolver):
                 self.speed.begin_epoch(self.step)
             if self.dither is not None:
                 self.dither.begin_epoch(self.step)             # the same epoch key as the speed factors'
+            if self.noise_reverb is not None:
+                self.noise_reverb.begin_epoch(self.step)
             for data in self.tr_set:
                 # Pre-step : update tf_rate/lr_rate and do zero_grad
                 tf_rate = self.optimizer.pre_step(self.step)

@@ -1696,3 +1696,96 @@ def resample_rows(x, n_host, ratio_idx, ratios, scale=1.0):
                                            idx.ctypes.data, meta_dev.data_ptr() + 8 * B, B, rat.ctypes.data, taps,
                                            rat.shape[0], _p(y), ld_out, float(scale), _stream()), "resample_rows")
     return y, n_out
+
+
+REVERB_MAX_TAPS = 8192          # RM_MAX_TAPS of csrc/reverb_mix.hip
+
+
+class RirBank:
+    """Room impulse responses resident on the device: taps [R, ld_r] float32 (rows zero padded), with every response's
+    length and peak - the first index of its largest |h| - on the host and, in one int32 tensor, on the device.  Built
+    once from a list of 1-D arrays of 1..8192 samples; ops.reverb_mix reads rows of it."""
+
+    def __init__(self, responses, device="cuda"):
+        hs = [np.ascontiguousarray(np.asarray(h, dtype=np.float32).reshape(-1)) for h in responses]
+        if not hs:
+            raise ValueError("RirBank: no impulse response")
+        for h in hs:
+            if not 1 <= h.shape[0] <= REVERB_MAX_TAPS or not np.all(np.isfinite(h)):
+                raise ValueError("RirBank: an impulse response has 1..%d finite samples, got %d"
+                                 % (REVERB_MAX_TAPS, h.shape[0]))
+        self.lens = np.asarray([h.shape[0] for h in hs], dtype=np.int32)
+        self.peaks = np.asarray([int(np.argmax(np.abs(h))) for h in hs], dtype=np.int32)
+        self.ld = (int(self.lens.max()) + 3) // 4 * 4
+        host = np.zeros((len(hs), self.ld), dtype=np.float32)
+        for r, h in enumerate(hs):
+            host[r, :h.shape[0]] = h
+        self.taps = torch.from_numpy(host).to(device)
+        self.meta = torch.from_numpy(np.concatenate([self.lens, self.peaks])).to(device)      # lens | peaks
+
+    def __len__(self):
+        return int(self.lens.shape[0])
+
+
+def reverb_mix(x, n_host, bank=None, rir_idx=None, noise=None, m_host=None, snr_lin=None, scale=1.0):
+    """Reverberation and additive noise for every row of a padded waveform batch (csrc/reverb_mix.hip; semantics:
+    include/asrk.h asrk_reverb_mix_f32).  x [B, ld_in] int16 or float32 on the GPU, n_host [B] the rows' sample counts;
+    bank: a RirBank (None: no reverberation) and rir_idx [B] the rows' responses, -1 for none; noise [B, ld_v] of x's
+    dtype on x's device (None: no noise), m_host [B] the samples each noise row holds (0: none; shorter than the
+    utterance: tiled circularly) and snr_lin [B] = 10^(snr_dB / 10); all index and length arrays ON THE HOST.
+    -> out [B, roundup4(max n)] float32, already multiplied by `scale`, columns beyond a row's length left unwritten.
+    Nothing is read back from the device."""
+    _require_gpu(x)
+    if x.dim() != 2 or x.dtype not in (torch.int16, torch.float32) or not x.is_contiguous():
+        raise ValueError("reverb_mix expects a contiguous [B, ld_in] int16 or float32 batch")
+    B, ld_in = x.shape
+    n = np.ascontiguousarray(np.asarray(n_host, dtype=np.int64).reshape(-1))
+    idx = np.full(B, -1, dtype=np.int32) if rir_idx is None else \
+        np.ascontiguousarray(np.asarray(rir_idx, dtype=np.int32).reshape(-1))
+    m = np.zeros(B, dtype=np.int64) if m_host is None else \
+        np.ascontiguousarray(np.asarray(m_host, dtype=np.int64).reshape(-1))
+    snr = np.ones(B, dtype=np.float32) if snr_lin is None else \
+        np.ascontiguousarray(np.asarray(snr_lin, dtype=np.float32).reshape(-1))
+    if not (n.shape[0] == idx.shape[0] == m.shape[0] == snr.shape[0] == B):
+        raise ValueError("reverb_mix: %d rows, %d lengths, %d response indices, %d noise lengths, %d ratios"
+                         % (B, n.shape[0], idx.shape[0], m.shape[0], snr.shape[0]))
+    if bank is None and B and idx.max() >= 0:
+        raise ValueError("reverb_mix: a row asks for an impulse response and no bank was given")
+    if bank is not None and bank.taps.device != x.device:
+        raise ValueError("reverb_mix: the bank lives on %s, the batch on %s" % (bank.taps.device, x.device))
+    if noise is None:
+        if B and m.max() > 0:
+            raise ValueError("reverb_mix: a row asks for noise and no noise batch was given")
+        ld_v = 0
+    else:
+        _require_gpu(noise)
+        if (noise.dim() != 2 or noise.shape[0] != B or noise.dtype != x.dtype or not noise.is_contiguous()
+                or noise.device != x.device):
+            raise ValueError("reverb_mix: noise must be a contiguous [B, ld_v] batch of x's dtype on x's device")
+        ld_v = noise.shape[1]
+    if B and not (np.all(np.isfinite(snr)) and snr.min() > 0.0):
+        raise ValueError("reverb_mix: snr_lin must be positive and finite")
+    ld_out = (int(n.max()) + 3) // 4 * 4 if B else 0
+    out = torch.empty((B, ld_out), dtype=torch.float32, device=x.device)
+    if B == 0:
+        return out
+    L = _L()
+    ws_bytes = int(L.asrk_reverb_mix_ws_bytes(B, int(max(n.max(), 0))))
+    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=x.device)
+    # the kernels' copies of the lengths, indices and ratios: one pinned buffer, one non-blocking upload
+    meta = torch.empty(3 * B, dtype=torch.int64).pin_memory()
+    meta[:B] = torch.from_numpy(n)
+    meta[B:2 * B] = torch.from_numpy(m)
+    meta[2 * B:].view(torch.int32)[:B] = torch.from_numpy(idx)
+    meta[2 * B:].view(torch.float32)[B:2 * B] = torch.from_numpy(snr)
+    md = meta.to(x.device, non_blocking=True)
+    base = md.data_ptr()
+    R = 0 if bank is None else len(bank)
+    _lib.check(L.asrk_reverb_mix_f32(
+        _p(x), x.element_size(), ld_in, n.ctypes.data, base,
+        None if bank is None else _p(bank.taps), 0 if bank is None else bank.ld,
+        None if bank is None else bank.lens.ctypes.data, None if bank is None else bank.meta.data_ptr(),
+        None if bank is None else bank.peaks.ctypes.data, None if bank is None else bank.meta.data_ptr() + 4 * R, R,
+        idx.ctypes.data, base + 16 * B, _p(noise), ld_v, m.ctypes.data, base + 8 * B, base + 20 * B, B, _p(out), ld_out,
+        float(scale), _p(ws), ws_bytes, _stream()), "reverb_mix")
+    return out

@@ -6,8 +6,10 @@ Same module names, constructor arguments, tensor shapes between stages ([C, D, T
 `torchaudio` is not required: 16-bit PCM wav is read with the stdlib `wave` module
 (torchaudio.load semantics: float32 in [-1, 1), [channel, samples]).
 """
+import collections
 import inspect
 import math
+import os
 import wave as _wave
 import zlib
 from fractions import Fraction
@@ -347,13 +349,18 @@ class ExtractAudioFeature(nn.Module):
         self.device = device
 
     def forward(self, filepath):
-        ''' filepath: a path, (waveform, sample_rate), (waveform, sample_rate, speed) or (waveform, sample_rate, speed,
-            dither_key).  With a speed (None: none) channel 0 of the waveform is speed-perturbed on the device first (the
-            kernel of the whole-batch form, B = 1).  The key matters only under dither > 0; without one a path gets the
-            evaluation key of seed 0 for its file name (Dither(.., 0).key(name, False)) and a tensor key 0. '''
-        speed, key = None, None
+        ''' filepath: a path, (waveform, sample_rate), (waveform, sample_rate, speed), (waveform, sample_rate, speed,
+            dither_key) or (waveform, sample_rate, speed, dither_key, corrupt).  With a speed (None: none) channel 0 of the
+            waveform is speed-perturbed on the device first (the kernel of the whole-batch form, B = 1).  The key matters
+            only under dither > 0; without one a path gets the evaluation key of seed 0 for its file name
+            (Dither(.., 0).key(name, False)) and a tensor key 0.  corrupt (None: none): the one-utterance Corruption of
+            NoiseReverb.draws - reverberation and noise on channel 0, behind the speed perturbation (ops.reverb_mix,
+            B = 1). '''
+        speed, key, corrupt = None, None, None
         if isinstance(filepath, (tuple, list)):
-            if len(filepath) == 4:
+            if len(filepath) == 5:      # .., corrupt: a one-utterance Corruption (NoiseReverb.draws) or None
+                waveform, sample_rate, speed, key, corrupt = filepath
+            elif len(filepath) == 4:
                 waveform, sample_rate, speed, key = filepath
             elif len(filepath) == 3:
                 waveform, sample_rate, speed = filepath
@@ -368,6 +375,10 @@ class ExtractAudioFeature(nn.Module):
             x = _f32c(waveform[0]).reshape(1, -1)
             y, n_out = ops.resample_rows(x, [x.shape[1]], [0], [SpeedPerturb.ratio(speed)], 1.0)
             waveform = y[:, :int(n_out[0])]
+        if corrupt is not None and corrupt.any():
+            # the whole-batch form's entry with B = 1, behind the speed perturbation: both routes see one waveform
+            x = _f32c(waveform[0]).reshape(1, -1)
+            waveform = corrupt.apply(x, [x.shape[1]], 1.0, int(sample_rate))[:, :x.shape[1]]
         extract = kaldi_fbank if self.mode == "fbank" else kaldi_mfcc
         y = extract(waveform, num_mel_bins=self.num_mel_bins, channel=-1,
                     sample_frequency=sample_rate, dither_key=0 if key is None else key, **self.kwargs)
@@ -462,7 +473,7 @@ class BatchFeatureTransform:
         win, shift = int(sample_rate * self.frame_length * 0.001), int(sample_rate * self.frame_shift * 0.001)
         return 0 if n_samples < win else 1 + (n_samples - win) // shift
 
-    def __call__(self, waves, sample_rate, speeds=None, dither_keys=None):
+    def __call__(self, waves, sample_rate, speeds=None, dither_keys=None, corrupt=None):
         """waves: list of 1-D int16 numpy arrays (raw PCM; uploaded as 2-byte samples) or float32 arrays /
         tensors in [-1, 1) -> (feat [B, Tmax, out_dim] on the device, zero padded, feat_len LongTensor [B]).
         speeds: one speed-perturbation factor per utterance (SpeedPerturb), or None.  Utterance b is resampled on the
@@ -470,9 +481,14 @@ class BatchFeatureTransform:
         of the PERTURBED waveform; None, or all factors 1.0, is the plain path: no extra launch, the same bits.
         dither_keys: one 64-bit key per utterance (Dither.key), required when the config's dither is > 0: the noise
         of utterance b is a pure function of dither_keys[b] and acts on the perturbed waveform; with dither 0 they are
-        ignored and the launches are the plain ones."""
+        ignored and the launches are the plain ones.
+        corrupt: the batch's reverberation / noise draws (NoiseReverb.draws), or None.  Applied behind the speed
+        perturbation and in front of the filterbank, whose dither then acts on the corrupted waveform; the lengths do
+        not change.  None, or draws that all say "nothing", is the plain path: no extra launch, the same bits."""
         L = _L()
         dev, B = self.device, len(waves)
+        if corrupt is not None and len(corrupt) != B:
+            raise ValueError('%d reverberation / noise draws for %d utterances' % (len(corrupt), B))
         if self.dither > 0.0 and (dither_keys is None or len(dither_keys) != B):
             raise ValueError('dither = %g needs one key per utterance: got %s for %d utterances'
                              % (self.dither, 'none' if dither_keys is None else len(dither_keys), B))
@@ -527,6 +543,10 @@ class BatchFeatureTransform:
         if perturb:
             # [B, nmax] PCM -> [B, ld] float32 waveforms at the perturbed speeds, already scaled
             wave, _ = ops.resample_rows(wave, ns_src, ridx, ratios, scale)
+            nmax, sbytes, scale = wave.shape[1], 4, 1.0
+        if corrupt is not None and corrupt.any():
+            # reverberation and noise on the (perturbed) waveforms: [B, nmax] -> [B, ld] float32, already scaled
+            wave = corrupt.apply(wave, ns, scale, int(sample_rate))
             nmax, sbytes, scale = wave.shape[1], 4, 1.0
         offs = np.zeros(B + 1, dtype=np.int64)
         offs[1:] = np.cumsum(ms)
@@ -812,6 +832,261 @@ class Dither:
     def create_msg(self):
         return 'Dither     | amplitude = {:g} of the [-1, 1) waveform ({:g} on the int16 scale) | per (frame, position), ' \
                'keyed by utterance and epoch; fixed for dev / test'.format(self.amplitude, self.amplitude * 32768.0)
+
+
+def scan_audio_dir(path):
+    """every .wav / .flac file under `path` (recursively), sorted by its path relative to `path`"""
+    found = []
+    for root, _, files in os.walk(str(path)):
+        for f in files:
+            if f.lower().endswith(('.wav', '.flac')):
+                found.append(os.path.relpath(os.path.join(root, f), str(path)))
+    return [os.path.join(str(path), r) for r in sorted(found)]
+
+
+def load_rir(filepath, max_taps):
+    """-> (float32 [K] of channel 0, K = min(samples, max_taps); sample_rate).  ValueError, with the file named, for an
+    empty or all-zero response and for one whose peak - the first index of the largest |h| of the WHOLE file - lies at
+    or beyond max_taps (truncation would cut the direct sound off)."""
+    q, sr = load_pcm(filepath)
+    h = q.astype(np.float32) / np.float32(32768.0)
+    if h.shape[0] == 0 or not np.any(h):
+        raise ValueError('noise_reverb: %s holds no impulse response (empty or all zero)' % filepath)
+    peak = int(np.argmax(np.abs(h)))
+    if peak >= max_taps:
+        raise ValueError('noise_reverb: the peak of %s lies at sample %d, beyond max_taps = %d'
+                         % (filepath, peak, max_taps))
+    return np.ascontiguousarray(h[:max_taps]), sr
+
+
+Draw = collections.namedtuple('Draw', 'rir noise offset snr_db')     # rir / noise: file index or -1; offset in [0, 1)
+
+
+class Corruption:
+    """the draws of one batch with the policy that made them: what BatchFeatureTransform's `corrupt=` takes"""
+
+    def __init__(self, policy, draws):
+        self.policy, self.draws = policy, list(draws)
+
+    def __len__(self):
+        return len(self.draws)
+
+    def any(self):
+        return any(d.rir >= 0 or d.noise >= 0 for d in self.draws)
+
+    def apply(self, wave, ns, scale, sample_rate):
+        """wave [B, ld] int16 or float32 on the GPU (row b holds ns[b] samples) -> the corrupted float32 batch, already
+        multiplied by `scale` (one ops.reverb_mix call; the noise rows are of wave's type and go up in one upload)"""
+        pol, B = self.policy, len(self.draws)
+        if wave.shape[0] != B:
+            raise ValueError('%d draws for %d utterances' % (B, wave.shape[0]))
+        bank = pol.bank(wave.device, sample_rate) if any(d.rir >= 0 for d in self.draws) else None
+        noise, ms = None, [0] * B
+        if any(d.noise >= 0 for d in self.draws):
+            host, ms = pol.noise_rows(self.draws, ns, wave.dtype == torch.int16, sample_rate)
+            noise = host.to(wave.device, non_blocking=True)
+            pol.mark_upload()
+        snr = [10.0 ** (d.snr_db / 10.0) for d in self.draws]
+        return ops.reverb_mix(wave, ns, bank, [d.rir for d in self.draws], noise, ms, snr, scale)
+
+
+class NoiseReverb:
+    """Multi-condition training (the Kaldi / LibriSpeech recipe): an utterance is convolved with a room impulse response
+    and a noise recording is added at a drawn signal-to-noise ratio, on the batch while it sits in HBM
+    (ops.reverb_mix -> csrc/reverb_mix.hip, semantics in include/asrk.h).  The utterance keeps its length.
+
+    rir:   {path, prob, max_taps}: every .wav / .flac under `path` (recursively, sorted, first channel), truncated to
+           max_taps <= 8192 samples; loaded and checked when the policy is built, uploaded once.
+    noise: {path, prob, snr_db: [lo, hi]}: files are decoded when first drawn and kept in a bounded host cache; the row
+           that goes up starts at a drawn offset and holds min(utterance, file) samples - a shorter file is rotated to
+           the offset and tiled circularly by the kernel.
+    Either block may be absent.  All files must have the corpus' sample rate (checked against the first batch's rate for
+    the responses, per file for the noise; nothing is resampled).
+
+    The draw - response or none, which, noise or none, which, offset, SNR uniform in dB - is stateless and the same on
+    every data-parallel rank: a pure function of (seed, epoch_key, utterance name); `begin_epoch(key)` as for
+    SpeedPerturb."""
+
+    KEYS = ('rir', 'noise')
+    RIR_KEYS = ('path', 'prob', 'max_taps')
+    NOISE_KEYS = ('path', 'prob', 'snr_db')
+    TAG = 0x6E7276625F647277        # keeps the stream apart from SpeedPerturb.factor's and Dither.key's
+    MAX_TAPS = ops.REVERB_MAX_TAPS
+    CACHE_BYTES = 256 << 20         # decoded noise kept on the host
+
+    def __init__(self, rir=None, noise=None, seed=0):
+        self.seed, self.epoch_key = int(seed), 0
+        self.rir_prob, self.rir_files, self.rirs, self.rir_rate, self.max_taps = 0.0, [], [], None, self.MAX_TAPS
+        self.noise_prob, self.noise_files, self.snr_db = 0.0, [], (0.0, 0.0)
+        if rir is not None:
+            rir = self._block('rir', rir, self.RIR_KEYS)
+            self.rir_prob = self._prob('rir', rir.get('prob', 0.5))
+            mt = rir.get('max_taps', self.MAX_TAPS)
+            if isinstance(mt, bool) or not isinstance(mt, int) or not 1 <= mt <= self.MAX_TAPS:
+                raise ValueError('noise_reverb: rir.max_taps must be an integer in 1..%d, got %r' % (self.MAX_TAPS, mt))
+            self.max_taps = mt
+            self.rir_files = self._files('rir', rir)
+            for f in self.rir_files:
+                h, sr = load_rir(f, mt)
+                if self.rir_rate is None:
+                    self.rir_rate = sr
+                elif sr != self.rir_rate:
+                    raise ValueError('noise_reverb: %s is sampled at %d Hz, %s at %d Hz'
+                                     % (f, sr, self.rir_files[0], self.rir_rate))
+                self.rirs.append(h)
+        if noise is not None:
+            noise = self._block('noise', noise, self.NOISE_KEYS)
+            self.noise_prob = self._prob('noise', noise.get('prob', 0.5))
+            snr = noise.get('snr_db', [5.0, 20.0])
+            if (not isinstance(snr, (list, tuple)) or len(snr) != 2
+                    or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in snr)):
+                raise ValueError('noise_reverb: noise.snr_db must be [lo, hi], two finite numbers, got %r' % (snr,))
+            if snr[0] > snr[1]:
+                raise ValueError('noise_reverb: noise.snr_db has lo > hi: %r' % (snr,))
+            self.snr_db = (float(snr[0]), float(snr[1]))
+            self.noise_files = self._files('noise', noise)
+        self._bank, self._cache, self._cache_bytes = None, collections.OrderedDict(), 0
+        self._staging, self._staging_ev = {}, None
+
+    @staticmethod
+    def _block(name, block, keys):
+        if not isinstance(block, dict):
+            raise ValueError('noise_reverb: %s must be a mapping, got %r' % (name, block))
+        unknown = sorted(set(block) - set(keys))
+        if unknown:
+            raise ValueError('noise_reverb: unknown key(s) %s in %s (known: %s)' % (unknown, name, ', '.join(keys)))
+        return block
+
+    @staticmethod
+    def _prob(name, p):
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+            raise ValueError('noise_reverb: %s.prob must be a number in [0, 1], got %r' % (name, p))
+        return float(p)
+
+    @staticmethod
+    def _files(name, block):
+        path = block.get('path')
+        if not isinstance(path, str) or not os.path.isdir(path):
+            raise ValueError('noise_reverb: %s.path must be an existing directory, got %r' % (name, path))
+        files = scan_audio_dir(path)
+        if not files:
+            raise ValueError('noise_reverb: no .wav or .flac file under %s.path = %r' % (name, path))
+        return files
+
+    @classmethod
+    def from_config(cls, cfg, seed=0):
+        """cfg: the whole yaml config (a mapping); its top-level `noise_reverb:` block holds `enable`, `rir` and `noise`.
+        -> None when the block is absent or `enable: false`."""
+        block = cfg.get('noise_reverb') if cfg is not None else None
+        if block is None:
+            return None
+        if not isinstance(block, dict):
+            raise ValueError('noise_reverb: expected a mapping, got %r' % (block,))
+        block = dict(block)
+        enable = block.pop('enable', True)
+        if not isinstance(enable, bool):
+            raise ValueError('noise_reverb: enable must be true or false, got %r' % (enable,))
+        unknown = sorted(set(block) - set(cls.KEYS))
+        if unknown:
+            raise ValueError('noise_reverb: unknown key(s) %s (known: enable, %s)' % (unknown, ', '.join(cls.KEYS)))
+        policy = cls(seed=seed, **block)                        # a disabled block is still checked
+        return policy if enable else None
+
+    def begin_epoch(self, epoch_key):
+        self.epoch_key = int(epoch_key)
+
+    def draw(self, name):
+        """the Draw of utterance `name` in the current epoch.  Six uniforms are taken whether they are used or not, so
+        no decision depends on which of the others were active."""
+        z = _splitmix64((self.seed & _M64) ^ _splitmix64(self.epoch_key & _M64) ^ zlib.crc32(name.encode()) ^ self.TAG)
+        u = [(_splitmix64((z + i) & _M64) >> 11) / float(1 << 53) for i in range(6)]
+        rir = min(int(u[1] * len(self.rirs)), len(self.rirs) - 1) if self.rirs and u[0] < self.rir_prob else -1
+        nf = len(self.noise_files)
+        noise = min(int(u[3] * nf), nf - 1) if nf and u[2] < self.noise_prob else -1
+        lo, hi = self.snr_db
+        return Draw(rir, noise, u[4], min(max(lo + u[5] * (hi - lo), lo), hi))
+
+    def draws(self, names):
+        """-> the Corruption of a batch of utterance names (BatchFeatureTransform's `corrupt=`)"""
+        return Corruption(self, [self.draw(n) for n in names])
+
+    def bank(self, device, sample_rate):
+        """the responses on the device (uploaded on first use); ValueError when their rate is not the corpus'"""
+        if self.rir_rate != sample_rate:
+            raise ValueError('noise_reverb: %s is sampled at %d Hz, the corpus at %d Hz (nothing is resampled)'
+                             % (self.rir_files[0], self.rir_rate, sample_rate))
+        if self._bank is None or self._bank.taps.device != torch.device(device):
+            self._bank = ops.RirBank(self.rirs, device)
+        return self._bank
+
+    def noise_pcm(self, index, sample_rate):
+        """int16 samples of noise file `index` through the bounded host cache (least recently used files leave)"""
+        hit = self._cache.get(index)
+        if hit is not None:
+            self._cache.move_to_end(index)
+            return hit
+        path = self.noise_files[index]
+        q, sr = load_pcm(path)
+        if sr != sample_rate:
+            raise ValueError('noise_reverb: %s is sampled at %d Hz, the corpus at %d Hz (nothing is resampled)'
+                             % (path, sr, sample_rate))
+        self._cache[index] = q
+        self._cache_bytes += q.nbytes
+        while self._cache_bytes > self.CACHE_BYTES and len(self._cache) > 1:
+            _, old = self._cache.popitem(last=False)
+            self._cache_bytes -= old.nbytes
+        return q
+
+    @staticmethod
+    def fill_row(row, pcm, n, offset):
+        """row[:m] = the m = min(n, len(pcm)) samples of `pcm` from int(offset * len(pcm)) on, wrapping at its end
+        (a file shorter than the utterance: the whole file rotated to the offset) -> m"""
+        Lf = int(pcm.shape[0])
+        m = min(int(n), Lf)
+        if m > 0:
+            start = min(int(offset * Lf), Lf - 1)
+            first = min(m, Lf - start)
+            row[:first] = pcm[start:start + first]
+            row[first:m] = pcm[:m - first]
+        return m
+
+    def noise_rows(self, draws, ns, as_int16, sample_rate):
+        """-> (pinned host tensor [B, max m] of int16, or of float32 = int16 / 32768; m per row).  The buffer is
+        persistent: the previous batch's upload is waited for before it is refilled."""
+        pcm = [None if d.noise < 0 else self.noise_pcm(d.noise, sample_rate) for d in draws]
+        ms = [0 if q is None else min(int(n), int(q.shape[0])) for q, n in zip(pcm, ns)]
+        B, ld = len(draws), max(max(ms), 1)
+        tdt = torch.int16 if as_int16 else torch.float32
+        st = self._staging.get(tdt)
+        if self._staging_ev is not None:
+            self._staging_ev.synchronize()
+            self._staging_ev = None
+        if st is None or st.numel() < B * ld:
+            st = torch.empty((B * ld + B * ld // 4,), dtype=tdt).pin_memory()
+            self._staging[tdt] = st
+        host_t = st[:B * ld].view(B, ld)
+        host = host_t.numpy()
+        for b, (q, d) in enumerate(zip(pcm, draws)):
+            if q is None:
+                continue
+            if as_int16:
+                self.fill_row(host[b], q, ns[b], d.offset)
+            else:
+                tmp = np.empty(ms[b], dtype=np.int16)
+                self.fill_row(tmp, q, ns[b], d.offset)
+                host[b, :ms[b]] = tmp.astype(np.float32) / np.float32(32768.0)
+        return host_t, ms
+
+    def mark_upload(self):
+        ev = torch.cuda.Event()
+        ev.record()
+        self._staging_ev = ev
+
+    def create_msg(self):
+        return 'NoiseReverb| {} RIR(s) <= {} taps, prob = {:g} | {} noise file(s), prob = {:g}, SNR in [{:g}, {:g}] dB ' \
+               '| drawn per utterance and epoch, the same on every rank' \
+            .format(len(self.rirs), self.max_taps, self.rir_prob, len(self.noise_files), self.noise_prob,
+                    self.snr_db[0], self.snr_db[1])
 
 
 def create_transform(audio_config, device='cuda'):

@@ -86,8 +86,8 @@ class _Speeds:
     ''' what the collate function asks of a SpeedPerturb policy and a Dither policy (src/audio.py), or of none: the
         factor of a file, its sample count after perturbation, its dither key, and the per-file chain's input for it '''
 
-    def __init__(self, policy, dither=None, train=False):
-        self.policy, self.dither, self.train = policy, dither, train
+    def __init__(self, policy, dither=None, train=False, corrupt=None):
+        self.policy, self.dither, self.train, self.corrupt = policy, dither, train, corrupt
 
     def factor(self, path):
         return self.policy.factor(_utt_name(path))
@@ -102,20 +102,28 @@ class _Speeds:
         ''' BatchFeatureTransform's dither_keys for these files: None without a Dither policy '''
         return None if self.dither is None else [self.key(p) for p in paths]
 
+    def draws(self, paths):
+        ''' BatchFeatureTransform's corrupt for these files: None without a NoiseReverb policy '''
+        return None if self.corrupt is None else self.corrupt.draws([_utt_name(p) for p in paths])
+
     def plain(self):
-        return self.policy is None and self.dither is None
+        return self.policy is None and self.dither is None and self.corrupt is None
 
     def wav(self, path):
         ''' load_wav's (waveform, sample_rate), with the file's factor appended under a policy (ExtractAudioFeature
             then resamples on the device: the per-file chain never drops the augmentation), and its dither key behind
-            that under a Dither policy (the factor is then None without a speed policy) '''
+            that under a Dither policy (the factor is then None without a speed policy), and the file's reverberation /
+            noise draw behind both under a NoiseReverb policy (factor and key are then None without their policies) '''
+        if self.corrupt is not None:
+            return load_wav(path) + (None if self.policy is None else self.factor(path),
+                                     None if self.dither is None else self.key(path), self.draws([path]))
         if self.dither is not None:
             return load_wav(path) + (None if self.policy is None else self.factor(path), self.key(path))
         return load_wav(path) if self.policy is None else load_wav(path) + (self.factor(path),)
 
 
 def collect_audio_batch(batch, audio_transform, mode, n_jobs=1, shard=None, speed_perturb=None, dither=None,
-                        train=False):
+                        train=False, noise_reverb=None):
     ''' [(audio_path, [token ids]), ...] (or one bucket of them) ->
         (names, feat [B,T,D] on the transform's device, feat_len [B], text [B,L])
         (reference: src/data.py:14-46).  shard = (rank, world): `batch` is the GLOBAL batch of a data-parallel step;
@@ -123,13 +131,15 @@ def collect_audio_batch(batch, audio_transform, mode, n_jobs=1, shard=None, spee
         speed_perturb: a SpeedPerturb policy (src/audio.py) or None; under a policy every length that decides something
         here - halving, dealing, the order within the batch, feat_len - is the PERTURBED one.
         dither: a Dither policy (src/audio.py) or None; every file's key is dither.key(name, train) on the whole-batch
-        path and on the per-file fallback alike (train: the training loader's epoch-keyed draw). '''
+        path and on the per-file fallback alike (train: the training loader's epoch-keyed draw).
+        noise_reverb: a NoiseReverb policy (src/audio.py) or None; every file's draw is noise_reverb.draw(name), on both
+        routes; no length changes. '''
     if type(batch[0]) is not tuple:
         batch = batch[0]
     paths = [str(b[0]) for b in batch]
     pool = _pool(n_jobs)
     bt = getattr(audio_transform, 'batch', None)
-    sp = _Speeds(speed_perturb, dither, train)
+    sp = _Speeds(speed_perturb, dither, train, noise_reverb)
     if bt is not None and os.environ.get('ASRK_BATCH_FBANK', '1') != '0':
         try:
             return _collect_audio_batch_device(batch, paths, bt, mode, pool, shard, sp)
@@ -219,8 +229,13 @@ def _collect_audio_batch_device(batch, paths, bt, mode, pool, shard=None, sp=_Sp
     with torch.no_grad():
         if sp.plain():
             audio_feat, audio_len = bt([pcm[i] for i in order], sr)
-        elif sp.dither is None:
+        elif sp.dither is None and sp.corrupt is None:
             audio_feat, audio_len = bt([pcm[i] for i in order], sr, speeds=[sp.factor(paths[i]) for i in order])
+        elif sp.corrupt is not None:
+            speeds = None if sp.policy is None else [sp.factor(paths[i]) for i in order]
+            audio_feat, audio_len = bt([pcm[i] for i in order], sr, speeds=speeds,
+                                       dither_keys=sp.keys([paths[i] for i in order]),
+                                       corrupt=sp.draws([paths[i] for i in order]))
         else:
             speeds = None if sp.policy is None else [sp.factor(paths[i]) for i in order]
             audio_feat, audio_len = bt([pcm[i] for i in order], sr, speeds=speeds,
@@ -310,11 +325,14 @@ def load_textset(n_jobs, use_gpu, pin_memory, corpus, text):
     return tr_set, dv_set, tokenizer.vocab_size, tokenizer, data_msg
 
 
-def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, speed_perturb=None, dither=None):
+def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, speed_perturb=None, dither=None,
+                 noise_reverb=None):
     ''' (reference: src/data.py:128-157) -> (tr_loader, dv_loader, feat_dim, vocab_size, tokenizer, msg).
         `use_gpu` must be true (there is no CPU feature path); `pin_memory` is accepted and unused.
         speed_perturb: a SpeedPerturb policy (src/audio.py) for the TRAINING loader's collate function, or None; the
         dev / test loaders never perturb.
+        noise_reverb: a NoiseReverb policy (src/audio.py) for the TRAINING loader's collate function, or None; dev and
+        test batches are never corrupted.
         dither: a Dither policy (src/audio.py) when audio['dither'] > 0, else None: it deals the keys of every loader;
         only the loader of a training split draws them per epoch, dev / test keys depend on (seed, name) alone.  A
         config with dither > 0 and no policy - the decoding solver, which passes none - gets the policy of the seed
@@ -340,7 +358,7 @@ def load_dataset(n_jobs, use_gpu, pin_memory, ascending, corpus, audio, text, sp
         sampler, shard = _dp_sampler(len(tr_set), tr_loader_bs, world, shuffle), (rank, world)
     collect_tr = partial(collect_audio_batch, audio_transform=audio_transform, mode=mode, n_jobs=n_jobs, shard=shard,
                          speed_perturb=speed_perturb if mode == 'train' else None, dither=dither,
-                         train=mode == 'train')
+                         train=mode == 'train', noise_reverb=noise_reverb if mode == 'train' else None)
     collect_dv = partial(collect_audio_batch, audio_transform=audio_transform, mode='test', n_jobs=n_jobs,
                          dither=dither)
     tr_set = DataLoader(tr_set, batch_size=tr_loader_bs, shuffle=shuffle and sampler is None,

@@ -956,6 +956,44 @@ int asrk_resample_rows_f32(const void *x, int sample_bytes, int64_t ld_in, const
                            const int32_t *ratios_host, const float *const *taps_host, int n_ratios, float *y,
                            int64_t ld_out, float scale, void *stream);
 
+/* ---- Reverberation and additive noise on the padded PCM batch (training input augmentation; sits behind
+ * asrk_resample_rows_f32 and in front of asrk_fbank_*_batch_f32, which then take out with sample_bytes = 4, scale = 1) ---
+ * x [B, ld_in] of int16 (sample_bytes 2) or f32 (sample_bytes 4), `scale` as in asrk_resample_rows_f32; row b holds n[b]
+ * samples: s[i] = x[b][i] * scale (one f32 rounding), s = 0 outside 0..n-1.  out [B, ld_out] f32.
+ * Impulse responses: rir [R, ld_r] f32 (device); response r has rir_len[r] = K taps, 1 <= K <= 8192, and
+ * rir_peak[r] = p, the first index of its largest |h| (the caller finds it).  rir_idx[b] in -1..R-1; -1 = no response,
+ * then y[i] = s[i] bit for bit; otherwise, for 0 <= i < n,
+ *     y[i] = sum_{k < K} h[k] * s[i + p - k]         (f32, fused multiply-adds in DESCENDING k, starting from 0):
+ * the direct sound stays where it was and the row keeps its length.
+ * Level: Ps = sum s[i]^2, Py = sum y[i]^2, Pv = sum v_i^2, each over i < n, each square and sum in float64 (of the f32
+ * values), through one partial per tile of 2048 samples in ws, added in tile order.  a = sqrt(Ps / Py) when
+ * rir_idx[b] >= 0 and Py > 0, else 1.
+ * Noise: v [B, ld_v], sample type and scale of x; row b holds m[b] samples, v_i = v[b][i mod m[b]] * scale (tiled
+ * circularly); m[b] == 0 = no noise.  snr_lin [B] f32 (device) = 10^(snr_dB / 10).  g = sqrt(Ps / (Pv * snr_lin)) when
+ * m > 0, Pv > 0, Ps > 0 and snr_lin is positive and finite, else 0.  a and g are computed in float64, rounded to f32
+ * (and kept at or under FLT_MAX).
+ *     out[b][i] = a * y[i] + g * v_i   for i < n   (f32: two products, one sum; no noise term when g == 0).
+ * Columns i >= n[b] of out are not written.  A row with neither a response nor noise is s bit for bit; a silent row
+ * stays exactly zero; no input of finite samples gives NaN or Inf.  A row's bits depend on that row alone (not on B,
+ * not on the other rows, not on ld_out), and two calls give the same bits: no atomics.
+ * n, m, rir_idx, rir_len and rir_peak are passed twice: the HOST arrays are checked and size the launch; the DEVICE
+ * copies are what the kernels read (clamped there to the buffers: a copy that disagrees cannot make them leave x, v, rir
+ * or out).  Two launches (convolution + partial sums; scale + mix), one when no row has a response or noise.
+ * ws: caller-owned device memory, 8-byte aligned, at least asrk_reverb_mix_ws_bytes(B, max_b n[b]) bytes
+ * (ASRK_EWORKSPACE if NULL or smaller), private to the call until the stream has passed it.
+ * ASRK_ESHAPE, all checked before any device call: a negative size, a leading dimension above 2^31 - 1, sample_bytes not
+ * 2 or 4, rir_len[r] outside 1..min(8192, ld_r), rir_peak[r] outside 0..rir_len[r]-1, rir_idx[b] outside -1..R-1,
+ * n[b] outside 0..min(ld_in, ld_out), m[b] outside 0..ld_v, out overlapping x or v, a misaligned ws, a NULL pointer with
+ * work to do (any host array it has to read; x, out, the device copies with a sample to compute; rir and its arrays
+ * with a response in use; v and snr_lin with noise in use).  B == 0, or no sample at all, returns 0 without a launch. */
+size_t asrk_reverb_mix_ws_bytes(int B, int64_t n_max);
+int asrk_reverb_mix_f32(const void *x, int sample_bytes, int64_t ld_in, const int64_t *n_host, const int64_t *n_dev,
+                        const float *rir, int64_t ld_r, const int32_t *rir_len_host, const int32_t *rir_len_dev,
+                        const int32_t *rir_peak_host, const int32_t *rir_peak_dev, int R, const int32_t *rir_idx_host,
+                        const int32_t *rir_idx_dev, const void *v, int64_t ld_v, const int64_t *m_host,
+                        const int64_t *m_dev, const float *snr_lin_dev, int B, float *out, int64_t ld_out, float scale,
+                        void *ws, size_t ws_bytes, void *stream);
+
 /* ---- CTC loss (bin/train_asr.py:49,123-124 -> torch.nn.CTCLoss(blank=0)) ---------------
  * log_probs element (t,b,c) at lp[t*stride_t + b*stride_b + c]; targets [B,L] int64 (row stride
  * tgt_stride) zero-padded; input_lengths/target_lengths int64 [B].

@@ -6,7 +6,7 @@ half-batch rule of src/data.py:22-24 cuts every batch whose first utterance is l
 what bench.py measures on a resident batch can be compared with what a user of main.py gets: file reads, the whole-batch
 fbank front end, collation, loss assembly, clipping, the update, logging cadence, everything.
 
-    python tools/solver_bench.py [--steps 20] [--warmup 6] [--workload cfg3|cfg2] [--specaug] [--speed]
+    python tools/solver_bench.py [--steps 20] [--warmup 6] [--workload cfg3|cfg2] [--specaug] [--speed] [--noise-reverb DIR]
 
 Prints one JSON line: ms/step of Solver.exec, ms/step of bench.py's step on a resident batch of the same shapes in the
 same process, and the host-side syncs the loop performed."""
@@ -67,6 +67,9 @@ def main():
     ap.add_argument("--specaug", action="store_true")
     # the same loop with the default speed perturbation (top-level `speed_perturb:` block) in the training collate
     ap.add_argument("--speed", action="store_true")
+    # the same loop with reverberation and noise (top-level `noise_reverb:` block): DIR holds rir/ and noise/, each
+    # with .wav / .flac files at the corpus' 16 kHz; either may be missing
+    ap.add_argument("--noise-reverb", metavar="DIR", default=None)
     args = ap.parse_args()
     bench = importlib.import_module("bench")
     w = bench.WORKLOADS[args.workload]
@@ -86,6 +89,14 @@ def main():
         cfg["specaug"] = {"enable": True}
     if args.speed:
         cfg["speed_perturb"] = {"enable": True}
+    if args.noise_reverb:
+        block = {"enable": True}
+        for sub in ("rir", "noise"):
+            if os.path.isdir(os.path.join(args.noise_reverb, sub)):
+                block[sub] = {"path": os.path.join(args.noise_reverb, sub)}
+        if len(block) == 1:
+            raise SystemExit("--noise-reverb: neither %s/rir nor %s/noise exists" % (args.noise_reverb, args.noise_reverb))
+        cfg["noise_reverb"] = block
     cfg_path = os.path.join(tmp, "cfg.yaml")
     yaml.safe_dump(cfg, open(cfg_path, "w"))
     main_mod = importlib.import_module(PKG + ".main")
@@ -147,7 +158,7 @@ def main():
     print(json.dumps({
         "what": "Solver.exec of bin/train_asr.py on a synthetic LibriSpeech-layout corpus (wav read + whole-batch fbank "
                 "front end + collate + model + losses + clip + Adadelta) vs bench.py's step on a resident batch",
-        "workload": args.workload, "specaug": bool(args.specaug), "speed_perturb": bool(args.speed), "batch_feat_shape": feat_shape, "batch_txt_shape": txt_shape,
+        "workload": args.workload, "specaug": bool(args.specaug), "speed_perturb": bool(args.speed), "noise_reverb": bool(args.noise_reverb), "batch_feat_shape": feat_shape, "batch_txt_shape": txt_shape,
         "steps": args.steps, "warmup": args.warmup,
         "solver_ms_per_step": dt * 1e3, "solver_frames_per_s": frames / dt,
         "bench_step_ms_per_step": dt_bench * 1e3, "bench_frames_per_s": w["B"] * w["T"] / dt_bench,
