@@ -42,6 +42,7 @@ void read_knobs() {
     k.gemm_nofast = env_present("ASRK_GEMM_NOFAST");
     k.split_w256 = env_int("ASRK_SPLIT_W256");
     k.split_tail = env_int("ASRK_SPLIT_TAIL");
+    k.split_mfma = env_int("ASRK_SPLIT_MFMA");
     k.fwd_mt = env_int("ASRK_FWD_MT");
     k.fwd_nt = env_int("ASRK_FWD_NT");
     k.rec_bf_mt4 = env_int("ASRK_REC_BF_MT4");

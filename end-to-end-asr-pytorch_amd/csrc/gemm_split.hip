@@ -676,6 +676,379 @@ int launch_split_gemm_w256(const SplitGemmArgs &a, int rb_b, hipStream_t s) {
     return ASRK_OK;
 }
 
+// ---------------------------------------------------------------------------------- 16x16x32 form of both bodies
+// The same tiles, panels, stage images and LDS-DMA pieces multiplied with v_mfma_f32_16x16x32_bf16 (half the length of
+// the 32x32x16 instruction, the chip holds a higher clock on it: DESIGN §3.10).  An operand fragment is one ds_read_b128
+// per lane: lane l holds row l & 15 of its 16-row tile and the eight k of 8-k chunk l >> 4, so a 16-lane group reads
+// 256 contiguous bytes of one 1-KiB piece and a wave instruction covers 32 k.  C/D: col = lane & 15, row = 4 (lane >> 4)
+// + reg.  A k step is 32 k: per 64 x 64 sub-tile six products of 4 x 4 MFMAs on seven 16-register fragment slots
+// (A0 twice, A1, A2, B0, B1, B2); every slot is refilled right after the product that retires it:
+//   p1 (A0,B2)  B0   of this step (the slot died with the previous p6)      p4 (A2,B0)  A0'  (other set)
+//   p2 (A1,B1)  -    then lgkmcnt(0) and the step's ONE barrier             p5 (A1,B0)  A2' B1'
+//   p3 (A0,B1)  B2'                                                         p6 (A0,B0)  A1'
+// (' = next step, read after the barrier from the next stage.)  Every fragment is requested at least two products
+// (512 cycles) before its first use.  Worker and DMA waves run the SAME loop and meet in the same barrier statement,
+// the role-specific work before and after it - the barrier counts cannot diverge for any nk.
+#define ASRK_P16(FA, FB, ACC, RD)                                                                          \
+    do {                                                                                                   \
+        _Pragma("unroll") for (int m = 0; m < 16; ++m) {                                                   \
+            ACC[m >> 2][m & 3] =                                                                           \
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA[m >> 2], FB[m & 3], ACC[m >> 2][m & 3], 0, 0, 0); \
+            __builtin_amdgcn_sched_barrier(0);                                                             \
+            RD(m);                                                                                         \
+            __builtin_amdgcn_sched_barrier(0);                                                             \
+        }                                                                                                  \
+    } while (0)
+
+// four fragments (16-row tiles 0..3 of one plane of one 64-row region) spread over a product: after MFMAs START,
+// START + STRIDE, ...  (The compiler waits with lgkmcnt(0) before the first use of a refilled slot, i.e. for EVERY read
+// issued so far: the reads ahead of such a point - a step's first product, and the explicit waits - end at least nine
+// MFMAs before it.)
+template <int START, int STRIDE>
+__device__ __forceinline__ void rd16_at(int m, bf16x8 (&slot)[4], const unsigned char *src) {
+    static_assert(START + 3 * STRIDE < 16, "inside one product");
+    const int i = (m - START) / STRIDE;
+    if (m >= START && i < 4 && START + i * STRIDE == m) slot[i] = *reinterpret_cast<const bf16x8 *>(src + i * 256);
+}
+__device__ __forceinline__ void rd16_all(bf16x8 (&slot)[4], const unsigned char *src) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) slot[i] = *reinterpret_cast<const bf16x8 *>(src + i * 256);
+}
+
+template <int P> struct StepSet { static constexpr int value = P; };
+
+// 128 x 128 tile: BK = 32 (one step per k-tile), three 48-KiB stages, 4 multiplying + 4 DMA waves (DMA wave d fills
+// region d: A rows 0..63, A rows 64..127, B rows 0..63, B rows 64..127).  64 accumulator + 112 fragment registers.
+template <bool SK>
+__global__ __launch_bounds__(512) void gemm_bf16x6_m16_kernel(SplitGemmArgs p) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
+    constexpr int NPL = 3, NC = 4, NST = 3, CHUNK = NPL * PIECE;
+    constexpr int REGION = NC * CHUNK, STAGE = 4 * REGION, LPT = NC * NPL;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntiles = p.tiles_m * p.tiles_n;
+    const int slice = SK ? blockIdx.x / ntiles : 0, bid = SK ? blockIdx.x - slice * ntiles : blockIdx.x;
+    const int kt0 = SK ? (int)((long)slice * p.nk / p.slices) : 0;
+    const int nk = SK ? (int)((long)(slice + 1) * p.nk / p.slices) - kt0 : p.nk;
+    const int q8 = ntiles >> 3, r8 = ntiles & 7, xcd = bid & 7, loc = bid >> 3;
+    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    constexpr int BAND = 8;
+    const int band = tile / (BAND * p.tiles_m);
+    const int band_w = min(BAND, p.tiles_n - band * BAND);
+    const int in_band = tile - band * BAND * p.tiles_m;
+    const int tm = in_band / band_w, tn = band * BAND + in_band % band_w;
+
+    const bool worker = wave < 4;
+    const int wr = worker ? wave >> 1 : 0, wc = wave & 1;
+    const int r0 = worker ? 0 : wave - 4;        // DMA role: the region this wave fills
+    const unsigned char *gsrc = (r0 < 2 ? p.Ap + (size_t)(tm * 2 + r0) * p.rb_stride_a
+                                        : p.Bp + (size_t)(tn * 2 + r0 - 2) * p.rb_stride_b) + (size_t)kt0 * REGION;
+    const unsigned voff = lane * 16;
+    unsigned char *ldst = lds + r0 * REGION;
+    auto issue = [&](int kt, int stage) {
+        const unsigned char *g = gsrc + (size_t)kt * REGION;
+        unsigned char *l = ldst + stage * STAGE;
+#pragma unroll
+        for (int j = 0; j < LPT; j += 4) glds16_run<4>(g + j * PIECE, voff, l + j * PIECE);
+    };
+
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+    const int frag_off = ((lane >> 4) * NPL) * PIECE + (lane & 15) * 16;
+    const unsigned char *abase = lds + wr * REGION + frag_off;
+    const unsigned char *bbase = lds + (2 + wc) * REGION + frag_off;
+    bf16x8 fa0[2][4], fa1[4], fa2[4], fb0[4], fb1[4], fb2[4];
+
+    if (!worker) {
+#pragma unroll
+        for (int s = 0; s < NST; ++s)
+            if (s < nk) issue(s, s);
+        const int later = min(NST - 1, nk - 1);  // tile 0 has landed once only the younger ones are outstanding
+        if (later >= 2) wait_vm<2 * LPT>();
+        else if (later == 1) wait_vm<LPT>();
+        else wait_vm<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+    if (worker) {
+        rd16_all(fa0[0], abase); rd16_all(fb2, bbase + 2 * PIECE);
+        rd16_all(fa1, abase + PIECE); rd16_all(fb1, bbase + PIECE); rd16_all(fa2, abase + 2 * PIECE);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    int stage = 0, kt = 0;
+    auto step = [&](auto set) {
+        constexpr int P = decltype(set)::value, Q = 1 - P;
+        int nstage = stage + 1;
+        if (nstage == NST) nstage = 0;
+        const unsigned char *bc = bbase + stage * STAGE;
+        const unsigned char *an = abase + nstage * STAGE, *bn = bbase + nstage * STAGE;
+        if (worker) {
+            auto rd1 = [&](int m) { rd16_at<0, 4>(m, fb0, bc); };
+            ASRK_P16(fa0[P], fb2, acc, rd1);
+            auto rd2 = [&](int) {};
+            ASRK_P16(fa1, fb1, acc, rd2);
+            wait_lgkm0();                        // my reads of this stage are done
+        } else {
+            // tile kt + 1 has landed once at most the one younger tile is outstanding
+            if (nk - 2 - kt >= 1) wait_vm<LPT>();
+            else wait_vm<0>();
+        }
+        __builtin_amdgcn_s_barrier();
+        if (worker) {
+            auto rd3 = [&](int m) { rd16_at<0, 4>(m, fb2, bn + 2 * PIECE); };
+            ASRK_P16(fa0[P], fb1, acc, rd3);
+            auto rd4 = [&](int m) { rd16_at<0, 4>(m, fa0[Q], an); };
+            ASRK_P16(fa2, fb0, acc, rd4);
+            auto rd5 = [&](int m) { rd16_at<0, 4>(m, fa2, an + 2 * PIECE); rd16_at<2, 4>(m, fb1, bn + PIECE); };
+            ASRK_P16(fa1, fb0, acc, rd5);
+            auto rd6 = [&](int m) { rd16_at<0, 2>(m, fa1, an + PIECE); };
+            ASRK_P16(fa0[P], fb0, acc, rd6);
+        } else if (kt + NST < nk) {
+            issue(kt + NST, stage);              // the stage every worker just left
+        }
+        stage = nstage;
+        ++kt;
+    };
+    while (kt < nk) {
+        step(StepSet<0>());
+        if (kt < nk) step(StepSet<1>());
+    }
+    if (!worker) return;
+
+    if constexpr (SK) {
+        // A lane holds four consecutive ROWS of one column: a 16-row strip of the wave tile (4 accumulators, 16 x 64)
+        // goes through a wave-private LDS image (row pitch 68 floats) and leaves as 16-byte stores, 256 contiguous
+        // bytes per workspace row.  Every wave is past the last barrier: all fragment reads that feed a product are
+        // done (what the last step fetched after its barrier is never used) and no LDS-DMA is outstanding.
+        constexpr int PITCH = 68;
+        static_assert(4 * 16 * PITCH * 4 <= STAGE, "transposition images fit one stage");
+        float *img = reinterpret_cast<float *>(lds) + wave * 16 * PITCH;
+        float *wsl = p.ws + (size_t)slice * p.M * p.ldw;
+        const int wrow0 = tm * 128 + wr * 64, wcol0 = tn * 128 + wc * 64;
+        wait_lgkm0();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) img[(4 * (lane >> 4) + r) * PITCH + j * 16 + (lane & 15)] = acc[i][j][r];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int idx = q * 64 + lane, rl = idx >> 4, c4 = (idx & 15) * 4;
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(img + rl * PITCH + c4);
+                const int row = wrow0 + i * 16 + rl, col = wcol0 + c4;
+                if (row < p.M && col < p.ldw) *reinterpret_cast<f32x4 *>(wsl + (size_t)row * p.ldw + col) = v;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the next strip rewrites the image
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        return;
+    }
+    const int row0 = tm * 128 + wr * 64 + 4 * (lane >> 4), col0 = tn * 128 + wc * 64 + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + j * 16;
+        if (col >= p.N) continue;
+        float bsum = 0.f;
+        if (p.bias) bsum += p.bias[col];
+        if (p.bias2) bsum += p.bias2[col];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + i * 16 + r;
+                if (row >= p.M) continue;
+                float *c = p.C + (size_t)row * p.ldc + col;
+                float v = p.alpha * acc[i][j][r] + bsum;
+                if (p.beta != 0.f) v += p.beta * *c;
+                *c = v;
+            }
+    }
+}
+
+// 128 x 256 tile: the panels' 16-k stages pair up into 32-k steps - lanes 0..31 read chunks 0 and 1 from the pair's
+// first stage, lanes 32..63 chunks 2 and 3 from its second (per-lane addresses, one instruction).  128 accumulator
+// registers leave room for ONE 64-column half of B beside A's three planes: a step is two column halves, the second
+// half's B fragments refill the slots the first half's products retire, the next step's A and first B half refill
+// under the second half.  Reads inside the products (h = column half, ' = next step):
+//   h0: p1 B0(h0)  p2 B2(h1)  p4 B1(h1)      h1: p1 B0(h1)  p2 -, barrier  p3 B2'(h0)  p4 A0'  p5 A2' B1'(h0)  p6 A1'
+// A stage pair is read from the middle of one step to the middle of the next and is refilled after that: the ring is
+// two pairs deep, the DMA waves have one 32-k step (~3 k cycles) of lead and wait for everything they issued
+// (vmcnt 0) before each barrier.
+template <int NDW>
+__global__ __launch_bounds__((4 + NDW) * 64) void gemm_bf16x6_w256_m16_kernel(SplitGemmArgs p, int rb_b, int BAND) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
+    constexpr int NPL = 3, NC = 2, CHUNK = NPL * PIECE;
+    constexpr int REGION = NC * CHUNK, NRG = 6, STAGE = NRG * REGION, PAIR = 2 * STAGE;
+    constexpr int LPT = NRG * NC * NPL / NDW, NRUN = LPT / 3;
+    static_assert(LPT * NDW == NRG * NC * NPL && NRUN * 3 == LPT, "36 pieces per stage, runs of three");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntiles = p.tiles_m * p.tiles_n, bid = blockIdx.x;
+    const int q8 = ntiles >> 3, r8 = ntiles & 7, xcd = bid & 7, loc = bid >> 3;
+    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    const int band = tile / (BAND * p.tiles_m);
+    const int band_w = min(BAND, p.tiles_n - band * BAND);
+    const int in_band = tile - band * BAND * p.tiles_m;
+    const int tm = in_band / band_w, tn = band * BAND + in_band % band_w;
+    const int ns = p.nk >> 1;                    // 32-k steps (p.nk counts 16-k stages and is even)
+
+    const bool worker = wave < 4;
+    // DMA role: wave d fills pieces [d * LPT, (d + 1) * LPT) of every stage, as runs of three (gemm_bf16x6_w256_kernel)
+    const int first = (worker ? 0 : wave - 4) * LPT;
+    const unsigned char *run_g[NRUN];
+#pragma unroll
+    for (int k = 0; k < NRUN; ++k) {
+        const int idx = first + 3 * k, r = idx / (NC * NPL), j = idx - r * (NC * NPL);
+        run_g[k] = (r < 2 ? p.Ap + (size_t)(tm * 2 + r) * p.rb_stride_a
+                          : p.Bp + (size_t)min(tn * 4 + r - 2, rb_b - 1) * p.rb_stride_b) + j * PIECE;
+    }
+    const unsigned voff = lane * 16;
+    unsigned char *ldst = lds + first * PIECE;
+    auto issue_pair = [&](int s, int slot) {     // 32-k step s = 16-k stages 2 s and 2 s + 1 of the panels
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            unsigned char *l = ldst + slot * PAIR + h * STAGE;
+            const size_t gk = (size_t)(2 * s + h) * REGION;
+#pragma unroll
+            for (int k = 0; k < NRUN; ++k) glds16_run<3>(run_g[k] + gk, voff, l + 3 * k * PIECE);
+        }
+    };
+
+    const int wr = worker ? wave >> 1 : 0, wc = wave & 1;
+    f32x4 acc0[4][4], acc1[4][4];                // column halves 0 / 1 of the 64 x 128 wave tile
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc0[i][j][r] = acc1[i][j][r] = 0.f;
+    const int frag_off = (lane >> 5) * STAGE + (((lane >> 4) & 1) * NPL) * PIECE + (lane & 15) * 16;
+    const unsigned char *abase = lds + wr * REGION + frag_off;
+    const unsigned char *bbase = lds + (2 + wc * 2) * REGION + frag_off;    // half h: + h * REGION
+    bf16x8 fa0[2][4], fa1[4], fa2[4], fb0[4], fb1[4], fb2[4];
+
+    if (!worker) {
+        issue_pair(0, 0);
+        if (ns > 1) {
+            issue_pair(1, 1);
+            wait_vm<2 * LPT>();                  // pair 0 has landed
+        } else {
+            wait_vm<0>();
+        }
+    }
+    __builtin_amdgcn_s_barrier();
+    if (worker) {
+        rd16_all(fa0[0], abase); rd16_all(fb2, bbase + 2 * PIECE);
+        rd16_all(fa1, abase + PIECE); rd16_all(fb1, bbase + PIECE); rd16_all(fa2, abase + 2 * PIECE);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    int s = 0;
+    auto step = [&](auto set) {
+        constexpr int P = decltype(set)::value, Q = 1 - P;     // this step's pair slot and A0 set / the next step's
+        const unsigned char *bc = bbase + P * PAIR;
+        const unsigned char *an = abase + Q * PAIR, *bn = bbase + Q * PAIR;
+        auto rd0 = [&](int) {};
+        if (worker) {
+            auto rd1 = [&](int m) { rd16_at<0, 4>(m, fb0, bc); };
+            ASRK_P16(fa0[P], fb2, acc0, rd1);
+            auto rd2 = [&](int m) { rd16_at<0, 4>(m, fb2, bc + REGION + 2 * PIECE); };
+            ASRK_P16(fa1, fb1, acc0, rd2);
+            ASRK_P16(fa0[P], fb1, acc0, rd0);
+            auto rd4 = [&](int m) { rd16_at<0, 4>(m, fb1, bc + REGION + PIECE); };
+            ASRK_P16(fa2, fb0, acc0, rd4);
+            ASRK_P16(fa1, fb0, acc0, rd0);
+            ASRK_P16(fa0[P], fb0, acc0, rd0);
+            wait_lgkm0();                        // free here (last read 35 MFMAs ago): no wait behind the reads below
+            auto rd7 = [&](int m) { rd16_at<0, 4>(m, fb0, bc + REGION); };
+            ASRK_P16(fa0[P], fb2, acc1, rd7);
+            ASRK_P16(fa1, fb1, acc1, rd0);
+            wait_lgkm0();                        // my reads of this pair are done
+        } else {
+            wait_vm<0>();                        // pair s + 1 (issued a step ago) has landed
+        }
+        __builtin_amdgcn_s_barrier();
+        if (worker) {
+            auto rd9 = [&](int m) { rd16_at<0, 4>(m, fb2, bn + 2 * PIECE); };
+            ASRK_P16(fa0[P], fb1, acc1, rd9);
+            auto rd10 = [&](int m) { rd16_at<0, 4>(m, fa0[Q], an); };
+            ASRK_P16(fa2, fb0, acc1, rd10);
+            auto rd11 = [&](int m) { rd16_at<0, 4>(m, fa2, an + 2 * PIECE); rd16_at<2, 4>(m, fb1, bn + PIECE); };
+            ASRK_P16(fa1, fb0, acc1, rd11);
+            auto rd12 = [&](int m) { rd16_at<0, 2>(m, fa1, an + PIECE); };
+            ASRK_P16(fa0[P], fb0, acc1, rd12);
+        } else if (s + 2 < ns) {
+            issue_pair(s + 2, P);                // the pair every worker just left
+        }
+        ++s;
+    };
+    while (s < ns) {
+        step(StepSet<0>());
+        if (s < ns) step(StepSet<1>());
+    }
+    if (!worker) return;
+
+    const int row0 = tm * 128 + wr * 64 + 4 * (lane >> 4), col0 = tn * 256 + wc * 128 + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int col = col0 + j * 16;
+        if (col >= p.N) continue;
+        float bsum = 0.f;
+        if (p.bias) bsum += p.bias[col];
+        if (p.bias2) bsum += p.bias2[col];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + i * 16 + r;
+                if (row >= p.M) continue;
+                float *c = p.C + (size_t)row * p.ldc + col;
+                float v = p.alpha * (j < 4 ? acc0[i][j & 3][r] : acc1[i][j & 3][r]) + bsum;
+                if (p.beta != 0.f) v += p.beta * *c;
+                *c = v;
+            }
+    }
+}
+#undef ASRK_P16
+
+template <bool SK>
+int launch_split_gemm_m16(const SplitGemmArgs &a, hipStream_t s) {
+    constexpr int lds = 3 * 4 * 4 * 3 * PIECE;
+    auto kern = gemm_bf16x6_m16_kernel<SK>;
+    static AsrkLdsLatch latch;
+    ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(kern), lds));
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n * (SK ? a.slices : 1)), dim3(512), lds, s, a);
+    ASRK_LAUNCH_CHECK();
+    if (SK) {
+        const int64_t items = (int64_t)a.M * (a.ldw >> 2);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)asrk_div_up64(items, 256)), dim3(256), 0, s, a.ws,
+                           a.slices, a.M, a.N, a.ldw, a.alpha, a.beta, a.C, a.ldc, a.bias, a.bias2);
+        ASRK_LAUNCH_CHECK();
+    }
+    return ASRK_OK;
+}
+
+int launch_split_gemm_w256_m16(const SplitGemmArgs &a, int rb_b, hipStream_t s) {
+    constexpr int lds = 4 * 6 * 2 * 3 * PIECE;
+    auto kern = gemm_bf16x6_w256_m16_kernel<4>;
+    static AsrkLdsLatch latch;
+    ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(kern), lds));
+    const int band = 2;
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, s, a, rb_b, band);
+    ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
 // ---------------------------------------------------------------------------------- host side
 // No state here: the panel workspace is the caller's (asrk_gemm_ws_bytes), the split mode is a call flag.
 template <int NC, int NST, bool SPEC, int WM, bool SK = false>
@@ -701,6 +1074,8 @@ int launch_split_gemm(const SplitGemmArgs &a, hipStream_t s) {
 namespace {
 constexpr int SPLIT_NC = 4;                      // k-tile = 32
 constexpr int NPL = 3;                           // bf16 planes per operand
+// default MFMA shape: v_mfma_f32_16x16x32_bf16 for launches at least this many 32-k tiles deep, 32x32x16 below
+constexpr int SPLIT_MFMA16_MIN_NK = 48;
 
 struct PanelGeom {
     int KC, rb;                                  // 8-k groups per row (padded to the k-tile), 64-row blocks
@@ -762,7 +1137,15 @@ int run_panel_gemm(int M, int N, int nk, float alpha, const unsigned char *Ap, s
     a.tiles_m = asrk_div_up(M, 128); a.tiles_n = asrk_div_up(N, 128);
     a.alpha = alpha; a.beta = beta;
     a.slices = std::min(slices, nk); a.ldw = (N + 3) & ~3; a.ws = ws;
-    if (a.slices > 1) return launch_split_gemm<4, 3, true, 2, true>(a, s);
+    // MFMA shape of the multiplying body (same tiles, panels and routing either way): ASRK_SPLIT_MFMA = 16 / 32 sets
+    // it for every launch of the process.  Otherwise the measured rule: 16x16x32 from 48 k-tiles
+    // (K >= 1536) on - a 16x16 store instruction writes four 64-byte row segments instead of two 128-byte ones, and
+    // below ~1024 k that costs more than the higher clock returns (K = 80: 0.81 -> 1.0 ms) - and never for split-K,
+    // where the two shapes were within the run-to-run spread.
+    const bool m16 = kn.is_set(kn.split_mfma) ? kn.split_mfma == 16 : nk >= SPLIT_MFMA16_MIN_NK;
+    const bool m16_sk = kn.is_set(kn.split_mfma) && kn.split_mfma == 16;
+    const bool m16_128 = m16, m16_w256 = m16;
+    if (a.slices > 1) return m16_sk ? launch_split_gemm_m16<true>(a, s) : launch_split_gemm<4, 3, true, 2, true>(a, s);
     // 128 x 256 tiles (gemm_bf16x6_w256_kernel): a quarter fewer LDS bytes per MFMA; needs enough tiles to fill the
     // chip (>= 2 per CU) and at least two 64-row blocks of B per tile row to make the wider tile worth it
     const int w256 = kn.get(kn.split_w256, 1);
@@ -780,19 +1163,22 @@ int run_panel_gemm(int M, int N, int nk, float alpha, const unsigned char *Ap, s
             const int tm1 = (int)((tiles - rem) / tn);
             if (w256 == 1 && rem > 0 && rem * 10 < 6L * ncu && tm1 > 0 && tm1 < tm && kn.get(kn.split_tail, 1)) {
                 b.tiles_m = tm1; b.M = tm1 * 128;
-                int rc = launch_split_gemm_w256<4, 4>(b, 2 * asrk_div_up(N, 128), s);
+                int rc = m16_w256 ? launch_split_gemm_w256_m16(b, 2 * asrk_div_up(N, 128), s)
+                                  : launch_split_gemm_w256<4, 4>(b, 2 * asrk_div_up(N, 128), s);
                 if (rc != ASRK_OK) return rc;
                 SplitGemmArgs c = a;
                 c.Ap = a.Ap + (size_t)tm1 * 2 * a.rb_stride_a;
                 c.C = a.C + (size_t)tm1 * 128 * ldc;
                 c.M = M - tm1 * 128;
                 c.tiles_m = asrk_div_up(c.M, 128);
-                return launch_split_gemm<4, 3, true, 2>(c, s);
+                return m16_128 ? launch_split_gemm_m16<false>(c, s) : launch_split_gemm<4, 3, true, 2>(c, s);
             }
-            return launch_split_gemm_w256<4, 4>(b, 2 * asrk_div_up(N, 128), s);
+            return m16_w256 ? launch_split_gemm_w256_m16(b, 2 * asrk_div_up(N, 128), s)
+                            : launch_split_gemm_w256<4, 4>(b, 2 * asrk_div_up(N, 128), s);
         }
     }
-    return launch_split_gemm<4, 3, true, 2>(a, s);    // BK 32, 3 stages (144 KiB), DMA waves
+    // BK 32, 3 stages (144 KiB), DMA waves
+    return m16_128 ? launch_split_gemm_m16<false>(a, s) : launch_split_gemm<4, 3, true, 2>(a, s);
 }
 }  // namespace
 

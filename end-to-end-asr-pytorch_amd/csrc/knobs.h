@@ -15,6 +15,8 @@ struct AsrkKnobs {
     // gemm_split.hip
     int split_w256;       // ASRK_SPLIT_W256: 0 = never the 128x256-tile kernel, 1 (default) when the launch has >= 2 tiles per CU, 2 = whenever N >= 512
     int split_tail;       // ASRK_SPLIT_TAIL: 0 = the 128x256 kernel also takes a mostly empty last round (no 128x128 tail launch)
+    int split_mfma;       // ASRK_SPLIT_MFMA: 16 = every split-GEMM launch multiplies with v_mfma_f32_16x16x32_bf16, 32 = with
+                          // v_mfma_f32_32x32x16_bf16 (same tiles, same panels); unset = 16x16x32 for K >= 1536 without split-K
     // lstm_rec.hip
     int fwd_mt, fwd_nt;   // ASRK_FWD_MT / ASRK_FWD_NT: force a forward tile
     int rec_bf_mt4;       // ASRK_REC_BF_MT4: 0 = no 16-unit x 16-row forward plan at H = 1024
