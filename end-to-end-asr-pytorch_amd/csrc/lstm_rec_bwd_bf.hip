@@ -1,7 +1,9 @@
 // ------------------------------------------------------------------------------------------------
 // BPTT on the bf16 matrix cores (exact 3-way operand splitting; see lstm_rec_fwd_bf_kernel / gemm_split.hip).
-// Plan geometry: 16 units x 16 batch rows per workgroup (UB = 16, NT = 1), wave w contracts gate w:
-// rec[b, u] = sum_j dG[b, w*H + j] W_hh[w*H + j][u].  KS = H / 32 k-steps per wave, six
+// Plan geometry: 16 units x 16 batch rows per workgroup (UB = 16, NT = 1), wave w contracts the hidden-unit range
+// [w*H/4, (w+1)*H/4) of all four gates: rec[b, u] = sum_g sum_{j in range} dG[b, g*H + j] W_hh[g*H + j][u] - the
+// 16 producer workgroups of that range are all a wave waits for (one canary load per lane, as in the forward kernel).
+// KS = H / 32 k-steps per wave: k-step js is gate js / (KS/4), exchange k-step w*KS/4 + js % (KS/4); six
 // v_mfma_f32_16x16x32_bf16 each (f32 kernel: 8 v_mfma_f32_16x16x4_f32 per 32 k at twice the cycles).
 //  * W_hh^T slice as three bf16 planes = 6 B per weight (384 KiB per workgroup at H = 1024): the first NREG
 //    k-steps of every wave live in registers (12 VGPRs per k-step), the rest in LDS in fragment order;
@@ -20,7 +22,9 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int CH = 8;                        // k-steps in the fragment ring
     constexpr int KL = KS - NREG;                // LDS-resident k-steps per wave
+    constexpr int KQ = KS / 4;                   // k-steps of one gate in a wave's unit range
     static_assert(KS >= CH, "ring longer than the slice");
+    static_assert(KS % 4 == 0, "unit range of a wave is a whole number of k-steps");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ngroups = p.ndir * p.nbg;
     const int group = blockIdx.x % ngroups, wg = blockIdx.x / ngroups;
@@ -36,18 +40,20 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
     int *abort_flag = reinterpret_cast<int *>(stage_t + 4 * 3 * 2 * 16 * 16);
 
     const int m16 = lane & 15, q4 = lane >> 4;
-    // ---- W_hh^T slice: lane (unit m16, k-group q4) of wave w, k-step js: W_hh[w*H + js*32 + q4*8 + e][u0 + m16]
+    // ---- W_hh^T slice: lane (unit m16, k-group q4) of wave w, k-step js = (gate g, kq):
+    //      W_hh[g*H + (w*KQ + kq)*32 + q4*8 + e][u0 + m16]
     bf16x8_t areg[NREG > 0 ? NREG : 1][3];
     {
         const float *W = p.whh[dir];
-        const bool live = !GRU || wave < 3;
 #pragma unroll
         for (int js = 0; js < KS; ++js) {
+            const int gate = js / KQ;
+            const bool live = !GRU || gate < 3;
             unsigned h0[8], h1[8], h2[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int j = js * 32 + q4 * 8 + e;
-                split3(live ? W[((size_t)wave * H + j) * H + u0 + m16] : 0.f, h0[e], h1[e], h2[e]);
+                const int j = (wave * KQ + js % KQ) * 32 + q4 * 8 + e;
+                split3(live ? W[((size_t)gate * H + j) * H + u0 + m16] : 0.f, h0[e], h1[e], h2[e]);
             }
             u32x4 w0, w1, w2;
 #pragma unroll
@@ -86,7 +92,11 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
     const size_t step_floats = data_floats + (size_t)p.canw;
     float *xgroup = p.X + (size_t)group * p.T * step_floats;
     const unsigned voff = (m16 < nb && p.dbg_steps != -1) ? (unsigned)(lane * 16) : 0x7ff00000u;
-    const unsigned gate_base = (unsigned)(wave * gate_floats * 4);
+    // this wave's fragments: k-steps [wave*KQ, (wave+1)*KQ) of every gate; frag_off(js) is a compile-time constant
+    const unsigned frag_base = (unsigned)(wave * KQ * 3 * 1024);
+    auto frag_off = [](int js) { return (unsigned)(((js / KQ) * KS + js % KQ) * 3 * 1024); };
+    // their producers are the nwg / 4 workgroups of that unit range, 4 canary words each (one per producer wave)
+    const int can_lo = wave * p.nwg, can_cnt = p.nwg;
     // staging image: ((gate*3 + plane)*2 + half)*256 + n*16 + (unit & 7)*2
     unsigned char *st_w = stage + (ul >> 3) * 256 + bl * 16 + (ul & 7) * 2;
     // transposed image: ((gate*3 + plane)*2 + row half)*256 + unit*16 + (row & 7)*2
@@ -184,8 +194,8 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
             bool ok = true;
             for (int z = (p.poll_mode >> 8) & 0xff; z > 0; z -= 8) __builtin_amdgcn_s_sleep(8);
             ok = wait_canaries(reinterpret_cast<const unsigned *>(
-                                   xgroup + (size_t)(s - 1) * step_floats + data_floats),
-                               4 * p.nwg, p.err, lane, p.poll_mode);
+                                       xgroup + (size_t)(s - 1) * step_floats + data_floats) + can_lo,
+                               can_cnt, p.err, lane, p.poll_mode);
             REC_STAMP(7);
             bool bad = false;
             if (ok) {
@@ -194,7 +204,7 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
                         bf[c][pl] = __builtin_amdgcn_raw_buffer_load_b128(
-                            rs, voff, gate_base + (unsigned)((c * 3 + pl) * 1024), 0);
+                            rs, voff, frag_base + frag_off(c) + (unsigned)(pl * 1024), 0);
                 __builtin_amdgcn_sched_barrier(0);
                 REC_STAMP(1);
 #pragma unroll
@@ -207,7 +217,7 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
                             bf[js % CH][pl] = __builtin_amdgcn_raw_buffer_load_b128(
-                                rs, voff, gate_base + (unsigned)(((js + CH) * 3 + pl) * 1024), 0);
+                                rs, voff, frag_base + frag_off(js + CH) + (unsigned)(pl * 1024), 0);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -224,7 +234,7 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_bf_kernel(RecBwdArgs p) {
 #pragma unroll
                             for (int pl = 0; pl < 3; ++pl)
                                 bf[c][pl] = __builtin_amdgcn_raw_buffer_load_b128(
-                                    rs, voff, gate_base + (unsigned)(((c0 + c) * 3 + pl) * 1024), 16);
+                                    rs, voff, frag_base + frag_off(c0 + c) + (unsigned)(pl * 1024), 16);
                         __builtin_amdgcn_sched_barrier(0);
                         bool b2 = false;
 #pragma unroll
