@@ -168,6 +168,7 @@ SIGNATURES = {
     "asrk_col2im_cl_f32": (c_int, [c_vp, c_vp] + [c_int] * 10 + [c_i64] * 4 + [c_vp]),
     "asrk_conv_weight_reorder_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "asrk_conv3x3_supported": (c_int, [c_int] * 4),
+    "asrk_conv3x3_plan_info": (c_int, [c_int] * 6 + [c_vp, c_int]),
     "asrk_conv3x3_weight_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "asrk_conv3x3_f32": (c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp]),
     "asrk_conv3x3_wgrad_ws_bytes": (c_sz, [c_int] * 5),

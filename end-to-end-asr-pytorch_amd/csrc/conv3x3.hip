@@ -618,6 +618,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_reduce_kernel(const float *
 
 struct Plan3 {
     int TH, tiles_h, lds;
+    int thmax;                                    // weight gradient: the largest TH the LDS budget allows (else unused)
 };
 
 inline bool dims_ok(int B, int H, int W, int C, int Cout) {
@@ -663,8 +664,38 @@ inline Plan3 wgrad_plan(int B, int H, int W, int splits) {
             best = Plan3{th, tiles_h, wgrad_lds(th, W)};
         }
     }
+    best.thmax = thmax;
     return best;
 }
+
+// what a weight-gradient launch walks and needs: ONE place for the launchers, the *_ws_bytes functions and
+// asrk_conv3x3_plan_info.  Workgroup g of G walks tiles g, g + G, ...: most / fewest are the trip counts of that loop.
+struct WgradWork {
+    Plan3 q;
+    int ntiles, G, gy;                            // grid = (G, gy)
+    int most, fewest;                             // tiles walked by the busiest / the idlest workgroup
+    size_t part_floats, ws_bytes;                 // ws = part[part_floats] then bpart[G][Cout]
+};
+
+inline WgradWork wgrad_finish(Plan3 q, int B, int G_of_ntiles(int, int), int gy, size_t part_per_group, int Cout) {
+    WgradWork k;
+    k.q = q;
+    k.ntiles = B * q.tiles_h;
+    k.G = G_of_ntiles(k.ntiles, gy);
+    k.gy = gy;
+    k.most = asrk_div_up(k.ntiles, k.G);
+    k.fewest = k.ntiles / k.G;
+    k.part_floats = (size_t)k.G * part_per_group;
+    k.ws_bytes = (k.part_floats + (size_t)k.G * Cout) * sizeof(float);
+    return k;
+}
+
+inline WgradWork wgrad_work(int B, int H, int W, int C, int Cout) {
+    const int splits = (C / 64) * (Cout / 64);
+    return wgrad_finish(wgrad_plan(B, H, W, splits), B, wgrad_groups, splits, (size_t)splits * 9 * 4096, Cout);
+}
+
+inline dim3 fwd_grid(int B, int tiles_img) { return dim3((unsigned)(B * tiles_img)); }
 
 inline bool al16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
@@ -673,7 +704,7 @@ int launch_conv(const Args &a, int lds, hipStream_t s) {
     static AsrkLdsLatch latch;
     auto kern = conv3x3_kernel<COUT, RELU, Args>;
     ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(kern), 158 * 1024));
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.B * a.tiles_img)), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(kern, fwd_grid(a.B, a.tiles_img), dim3(256), lds, s, a);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
 }
@@ -737,10 +768,7 @@ extern "C" int asrk_conv3x3_len_f32(const float *x, const float *wf, const float
 
 extern "C" size_t asrk_conv3x3_wgrad_ws_bytes(int B, int H, int W, int C, int Cout) {
     if (!dims_ok(B, H, W, C, Cout) || B == 0) return 0;
-    const int splits = (C / 64) * (Cout / 64);
-    const Plan3 q = wgrad_plan(B, H, W, splits);
-    const int G = wgrad_groups(B * q.tiles_h, splits);
-    return ((size_t)G * splits * 9 * 4096 + (size_t)G * Cout) * sizeof(float);
+    return wgrad_work(B, H, W, C, Cout).ws_bytes;
 }
 
 extern "C" int asrk_conv3x3_wgrad_f32(const float *x, const float *dy, const float *ymask, float *dw, float *db, int B,
@@ -758,12 +786,11 @@ extern "C" int asrk_conv3x3_wgrad_f32(const float *x, const float *dy, const flo
     if (!asrk_conv3x3_supported(H, W, C, Cout) || !al16(x) || !al16(dy) || (ymask && !al16(ymask))) return ASRK_ESHAPE;
     if (!ws || ws_bytes < asrk_conv3x3_wgrad_ws_bytes(B, H, W, C, Cout)) return ASRK_EWORKSPACE;
     if (!al16(ws)) return ASRK_EINVAL;
-    const int splits = (C / 64) * (Cout / 64);
-    const Plan3 q = wgrad_plan(B, H, W, splits);
-    const int ntiles = B * q.tiles_h;
-    const int G = wgrad_groups(ntiles, splits);
+    const WgradWork k = wgrad_work(B, H, W, C, Cout);
+    const Plan3 q = k.q;
+    const int ntiles = k.ntiles, G = k.G, splits = k.gy;
     float *part = reinterpret_cast<float *>(ws);
-    float *bpart = part + (size_t)G * splits * 9 * 4096;
+    float *bpart = part + k.part_floats;
     W3Args a{x, dy, ymask, part, bpart, B, H, W, C, Cout, q.TH, q.tiles_h, ntiles, (q.TH * W + 1) & ~1};
     static AsrkLdsLatch latch;
     ASRK_HIP(asrk_max_lds_once(latch, reinterpret_cast<const void *>(conv3x3_wgrad_kernel), 158 * 1024));
@@ -788,7 +815,13 @@ inline Plan3 first_plan(int H, int W, int C, bool wgrad) {
     q.TH = std::max(1, std::min(H, 128 / W));
     q.tiles_h = asrk_div_up(H, q.TH);
     q.lds = C * (q.TH + 2) * (W + 2) * 4 + (wgrad ? 128 * CS * 4 + 128 * 4 : 0);
+    q.thmax = q.TH;
     return q;
+}
+inline dim3 first_grid(int B, const Plan3 &q, int Cout) { return dim3((unsigned)(B * q.tiles_h), (unsigned)(Cout / 64)); }
+inline int first_groups(int ntiles, int) { return std::max(1, std::min(ntiles, 1024)); }
+inline WgradWork first_work(int B, int H, int W, int C, int Cout) {
+    return wgrad_finish(first_plan(H, W, C, true), B, first_groups, Cout / 64, (size_t)Cout * 32, Cout);
 }
 }  // namespace
 
@@ -805,7 +838,7 @@ extern "C" int asrk_conv3x3_first_f32(const float *x, const float *w, const floa
     F1Args a{x, w, bias, y, nullptr, nullptr, nullptr, nullptr, B, H, W, C, Cout, q.TH, q.tiles_h, B * q.tiles_h, sb, sh, sw, sc};
     hipStream_t s = (hipStream_t)stream;
     asrk_prof_begin_(PROF_CONV, s);
-    const dim3 grid((unsigned)(B * q.tiles_h), (unsigned)(Cout / 64));
+    const dim3 grid = first_grid(B, q, Cout);
     if (relu) hipLaunchKernelGGL((conv3x3_first_kernel<true, F1Args>), grid, dim3(256), q.lds, s, a);
     else hipLaunchKernelGGL((conv3x3_first_kernel<false, F1Args>), grid, dim3(256), q.lds, s, a);
     asrk_prof_end_(PROF_CONV, s);
@@ -826,7 +859,7 @@ extern "C" int asrk_conv3x3_first_len_f32(const float *x, const float *w, const 
                 hlen};
     hipStream_t s = (hipStream_t)stream;
     asrk_prof_begin_(PROF_CONV, s);
-    const dim3 grid((unsigned)(B * q.tiles_h), (unsigned)(Cout / 64));
+    const dim3 grid = first_grid(B, q, Cout);
     if (relu) hipLaunchKernelGGL((conv3x3_first_kernel<true, F1LenArgs>), grid, dim3(256), q.lds, s, a);
     else hipLaunchKernelGGL((conv3x3_first_kernel<false, F1LenArgs>), grid, dim3(256), q.lds, s, a);
     asrk_prof_end_(PROF_CONV, s);
@@ -836,9 +869,7 @@ extern "C" int asrk_conv3x3_first_len_f32(const float *x, const float *w, const 
 
 extern "C" size_t asrk_conv3x3_first_wgrad_ws_bytes(int B, int H, int W, int C, int Cout) {
     if (!first_ok(B, H, W, C, Cout) || B == 0) return 0;
-    const Plan3 q = first_plan(H, W, C, true);
-    const int G = std::max(1, std::min(B * q.tiles_h, 1024));
-    return ((size_t)Cout * G * 32 + (size_t)G * Cout) * sizeof(float);
+    return first_work(B, H, W, C, Cout).ws_bytes;
 }
 
 extern "C" int asrk_conv3x3_first_wgrad_f32(const float *x, const float *dy, const float *ymask, float *dw, float *db, int B,
@@ -856,17 +887,40 @@ extern "C" int asrk_conv3x3_first_wgrad_f32(const float *x, const float *dy, con
     if (!first_ok(B, H, W, C, Cout) || !al16(dy) || (ymask && !al16(ymask))) return ASRK_ESHAPE;
     if (!ws || ws_bytes < asrk_conv3x3_first_wgrad_ws_bytes(B, H, W, C, Cout)) return ASRK_EWORKSPACE;
     if (!al16(ws)) return ASRK_EINVAL;
-    const Plan3 q = first_plan(H, W, C, true);
-    const int ntiles = B * q.tiles_h;
-    const int G = std::max(1, std::min(ntiles, 1024));
+    const WgradWork k = first_work(B, H, W, C, Cout);
+    const Plan3 q = k.q;
+    const int ntiles = k.ntiles, G = k.G;
     float *part = reinterpret_cast<float *>(ws);
-    float *bpart = part + (size_t)Cout * G * 32;
+    float *bpart = part + k.part_floats;
     F1Args a{x, nullptr, nullptr, nullptr, dy, ymask, part, bpart, B, H, W, C, Cout, q.TH, q.tiles_h, ntiles, sb, sh, sw, sc};
     asrk_prof_begin_(PROF_CONV, s);
-    hipLaunchKernelGGL(conv3x3_first_wgrad_kernel, dim3((unsigned)G, (unsigned)(Cout / 64)), dim3(256), q.lds, s, a);
+    hipLaunchKernelGGL(conv3x3_first_wgrad_kernel, dim3((unsigned)G, (unsigned)k.gy), dim3(256), q.lds, s, a);
     hipLaunchKernelGGL(conv3x3_first_reduce_kernel, dim3((unsigned)(Cout + Cout / 64)), dim3(256), 0, s, part, bpart, dw, db,
                        G, Cout, 9 * C);
     asrk_prof_end_(PROF_CONV, s);
     ASRK_LAUNCH_CHECK();
+    return ASRK_OK;
+}
+
+// ---- what the launches above would do for a shape, from their own planners; host only, no HIP call
+extern "C" int asrk_conv3x3_plan_info(int kind, int B, int H, int W, int C, int Cout, int *out, int n) {
+    if (!out || n < ASRK_CONV3X3_PLAN_INFO_LEN) return ASRK_EINVAL;
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    if (kind < 0 || kind > 3 || B < 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return ASRK_EINVAL;
+    const bool first = kind >= 2, wgrad = kind & 1;
+    const bool ok = first ? first_ok(B, H, W, C, Cout) : dims_ok(B, H, W, C, Cout) && asrk_conv3x3_supported(H, W, C, Cout);
+    if (!ok) return ASRK_OK;                      // out[0] == 0: the callers keep the im2col route
+    const auto fits = [](size_t v) { return (int)std::min(v, (size_t)0x7fffffff); };
+    out[0] = 1;
+    if (wgrad) {
+        const WgradWork k = first ? first_work(B, H, W, C, Cout) : wgrad_work(B, H, W, C, Cout);
+        out[1] = k.q.TH, out[2] = k.q.tiles_h, out[3] = k.ntiles, out[8] = k.q.lds, out[10] = k.q.thmax;
+        if (B > 0) out[4] = k.G, out[5] = k.gy, out[6] = k.most, out[7] = k.fewest, out[9] = fits(k.ws_bytes);
+        return ASRK_OK;
+    }
+    const Plan3 q = first ? first_plan(H, W, C, false) : fwd_plan(H, W);
+    const dim3 grid = first ? first_grid(B, q, Cout) : fwd_grid(B, q.tiles_h);
+    out[1] = q.TH, out[2] = q.tiles_h, out[3] = B * q.tiles_h, out[8] = q.lds, out[10] = q.TH;
+    if (B > 0) out[4] = (int)grid.x, out[5] = (int)grid.y, out[6] = out[7] = 1;
     return ASRK_OK;
 }

@@ -738,6 +738,23 @@ int asrk_conv_weight_reorder_f32(const float *src, float *dst, int Cout, int Cin
  *       aligned (ASRK_EWORKSPACE if smaller).
  * ASRK_ESHAPE: unsupported shape or a pointer that is not 16-byte aligned. */
 int asrk_conv3x3_supported(int H, int W, int C, int Cout);
+/* What the 3x3 launches do for a shape, from the planners the launches themselves use; host only (no device call, runs
+ * without a GPU; tests/test_conv_plan_cpu.py holds the convolution case table to it).
+ * kind: 0 asrk_conv3x3_f32 / _len_f32 (forward; the data gradient is kind 0 with C and Cout exchanged),
+ *       1 asrk_conv3x3_wgrad_f32, 2 asrk_conv3x3_first_f32 / _first_len_f32, 3 asrk_conv3x3_first_wgrad_f32.
+ * ASRK_EINVAL: out == NULL, n < ASRK_CONV3X3_PLAN_INFO_LEN, kind outside 0..3, B < 0 or a size <= 0 (as the launches);
+ * out[0..n) is zeroed first whenever out and n are valid.  Otherwise ASRK_OK and
+ *   [0] supported: what asrk_conv3x3_supported / asrk_conv3x3_first_supported and the launches' own size limits say;
+ *       0 leaves every other field 0 (the callers keep the im2col route)
+ *   [1] TH: the most image rows one tile can touch   [2] tiles per image   [3] tiles in all (B x [2])
+ *   [4] workgroups (grid x)   [5] grid y (kind 1: Cin/64 x Cout/64 splits; kinds 2, 3: 64-column blocks; kind 0: 1)
+ *   [6] the most and [7] the fewest tiles any workgroup walks (1 and 1 for the forward kinds)
+ *   [8] dynamic LDS bytes   [9] workspace bytes (= the *_wgrad_ws_bytes functions; 0 for the forward kinds; INT_MAX if larger)
+ *   [10] kind 1: thmax, the largest TH the LDS budget allows - the cost model chose a smaller one where [1] < [10];
+ *        other kinds: [1]
+ * B == 0 launches nothing: [4..7] and [9] are 0. */
+#define ASRK_CONV3X3_PLAN_INFO_LEN 12
+int asrk_conv3x3_plan_info(int kind, int B, int H, int W, int C, int Cout, int *out, int n);
 int asrk_conv3x3_weight_f32(const float *w, float *wf, int Cout, int Cin, int transpose, void *stream);
 int asrk_conv3x3_f32(const float *x, const float *xmask, const float *wf, const float *bias, float *y, int B, int H, int W,
                      int C, int Cout, int relu, void *stream);

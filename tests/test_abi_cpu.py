@@ -67,6 +67,29 @@ def test_argument_errors_without_gpu(lib):
     assert L.asrk_lstm_ws_bytes() >= 4096
 
 
+def test_conv3x3_plan_info_argument_checks(lib):
+    """host only: NULL / short record, kind outside 0..3, B < 0 and sizes <= 0 are ASRK_EINVAL as in the launches, with
+    the record zeroed; an unsupported shape is ASRK_OK with supported = 0"""
+    L = lib.load()
+    n = 12
+    out = (ctypes.c_int * n)()
+    assert L.asrk_conv3x3_plan_info(0, 2, 7, 40, 64, 64, None, n) == -1
+    assert L.asrk_conv3x3_plan_info(0, 2, 7, 40, 64, 64, out, n - 1) == -1
+    for kind in (-1, 4):
+        assert L.asrk_conv3x3_plan_info(kind, 2, 7, 40, 64, 64, out, n) == -1
+    z = ctypes.c_void_p(0)
+    for a in ((-1, 7, 40, 64, 64), (2, 0, 40, 64, 64), (2, 7, 0, 64, 64), (2, 7, 40, 0, 64), (2, 7, 40, 64, 0)):
+        for kind in range(4):
+            out[0] = 5
+            assert L.asrk_conv3x3_plan_info(kind, *a, out, n) == -1 and list(out) == [0] * n
+        assert L.asrk_conv3x3_f32(z, z, z, z, z, *a, 0, z) == -1
+        assert L.asrk_conv3x3_wgrad_f32(z, z, z, z, z, *a, z, 0, z) == -1
+    assert L.asrk_conv3x3_plan_info(0, 2, 7, 40, 64, 64, out, n) == 0 and out[0] == 1 and out[4] == 2 * 3
+    assert L.asrk_conv3x3_plan_info(0, 2, 7, 129, 64, 64, out, n) == 0 and list(out) == [0] * n
+    assert L.asrk_conv3x3_plan_info(2, 2, 7, 40, 4, 64, out, n) == 0 and list(out) == [0] * n
+    assert L.asrk_conv3x3_plan_info(3, 2, 7, 40, 3, 128, out, n) == 0 and out[0] == 1 and out[5] == 2
+
+
 def test_product_path_fails_loudly_without_gpu(pkg):
     import torch
     if torch.cuda.is_available():
