@@ -62,6 +62,8 @@ SIGNATURES = {
     "asrk_ctc_prefix_beam_multi_ws_bytes": (c_sz, [c_int, c_int, c_int, ctypes.POINTER(c_sz)]),
     "asrk_ctc_prefix_beam_multi_f32": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_f32,
                                                c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "asrk_ngram_step_f32": (c_int, [c_int] * 4 + [c_vp] * 8 + [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64,
+                                    c_int, c_vp]),
     "asrk_fbank_frames_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_int,
                                       c_vp]),
     "asrk_power_spectrum_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),

@@ -15,6 +15,7 @@ from torch import nn
 from .. import ops
 from .. import decoder_ops as dops
 from .lm import RNNLM
+from .ngram import NGramLM, is_ngram_path
 
 LOG_ZERO = -10000000.0  # Log-zero for CTC
 
@@ -178,20 +179,31 @@ class CTCBeamDecoder(nn.Module):
             self.device = device
             self.lm_w = lm_weight
             self.lm_path = lm_path
-            lm_config = yaml.load(open(lm_config, 'r'), Loader=yaml.FullLoader)
-            self.lm = RNNLM(self.asr.vocab_size, **lm_config['model']).to(self.device)
-            self.lm.load_state_dict(torch.load(self.lm_path, map_location='cpu')['model'])
+            if is_ngram_path(lm_path):              # back-off n-gram (ARPA / saved image): lm_config is not read
+                self.lm = NGramLM.from_file(lm_path, self.asr.vocab_size).to(self.device)
+            else:
+                lm_config = yaml.load(open(lm_config, 'r'), Loader=yaml.FullLoader)
+                self.lm = RNNLM(self.asr.vocab_size, **lm_config['model']).to(self.device)
+                self.lm.load_state_dict(torch.load(self.lm_path, map_location='cpu')['model'])
             self.lm.eval()
 
     def create_msg(self):
-        return ['Decode spec| CTC decoding \t| Beam size = {} \t| LM weight = {}'.format(
+        msg = ['Decode spec| CTC decoding \t| Beam size = {} \t| LM weight = {}'.format(
             self.beam_size, self.lm_w)]
+        if self.apply_lm and isinstance(self.lm, NGramLM):
+            msg += self.lm.create_msg()
+        return msg
+
+    def _lm_logp(self, lm_out):
+        ''' log-probabilities of an LM step: the RNN-LM returns logits; an LM with `returns_logp` (the n-gram) is
+            used as it is - a pruned back-off model is not normalised and renormalising would change it '''
+        return lm_out if getattr(self.lm, 'returns_logp', False) else ops.log_softmax(lm_out)
 
     def _lm_step(self, token, hidden):
         dev = self.device
         out, hid = self.lm(torch.full((1, 1), int(token), dtype=torch.long, device=dev),
                            torch.ones(1, dtype=torch.long), hidden)
-        logp = ops.log_softmax(out).reshape(-1)
+        logp = self._lm_logp(out).reshape(-1)
         return _LMOut(logp.cpu().numpy(), logp), hid
 
     def _device_search_ok(self, V):
@@ -267,7 +279,7 @@ class CTCBeamDecoder(nn.Module):
             states = list(hid) if lstm else [hid]                      # each [n_layers, rows, dim]
             pad = lambda x, dim: torch.cat([x, x.new_zeros(*x.shape[:dim], W - x.shape[dim], *x.shape[dim + 1:])],
                                            dim)
-            lm_rows = pad(ops.log_softmax(out).reshape(1, V), 0).contiguous()          # [W, V]
+            lm_rows = pad(self._lm_logp(out).reshape(1, V), 0).contiguous()            # [W, V]
             states = [pad(x, 1).contiguous() for x in states]
             _, _, _, p_off, l_off, g_off = offsets(0)
             cur = 0
@@ -281,7 +293,7 @@ class CTCBeamDecoder(nn.Module):
                     out, hid = self.lm(last.view(W, 1), torch.ones(W, dtype=torch.long),
                                        (h_in[0], h_in[1]) if lstm else h_in[0])
                     stepped = list(hid) if lstm else [hid]
-                    lm_rows = torch.cat([lm_rows, ops.log_softmax(out).reshape(W, V)], 0).index_select(0, gidx)
+                    lm_rows = torch.cat([lm_rows, self._lm_logp(out).reshape(W, V)], 0).index_select(0, gidx)
                     states = [torch.cat([o_, n_], 1).index_select(1, gidx) for o_, n_ in zip(states, stepped)]
         return read_back(cur)
 
@@ -331,7 +343,7 @@ class CTCBeamDecoder(nn.Module):
         out, hid = self.lm(torch.zeros((1, 1), dtype=torch.long, device=dev), torch.ones(1, dtype=torch.long), None)
         lstm = isinstance(hid, tuple)
         lm_rows = torch.zeros((U * W, V), dtype=torch.float32, device=dev)     # <sos> step -> row 0 of every utterance
-        lm_rows[0::W] = ops.log_softmax(out).reshape(1, V)
+        lm_rows[0::W] = self._lm_logp(out).reshape(1, V)
         states = []
         for x in (list(hid) if lstm else [hid]):                               # each [n_layers, rows, dim]
             st = x.new_zeros(x.shape[0], U * W, x.shape[2])
@@ -348,7 +360,7 @@ class CTCBeamDecoder(nn.Module):
                 h_in = [x.index_select(1, parent) for x in states]
                 out, hid = self.lm(last.view(U * W, 1), ones, (h_in[0], h_in[1]) if lstm else h_in[0])
                 stepped = list(hid) if lstm else [hid]
-                lm_rows = torch.cat([lm_rows, ops.log_softmax(out).reshape(U * W, V)], 0).index_select(0, gidx)
+                lm_rows = torch.cat([lm_rows, self._lm_logp(out).reshape(U * W, V)], 0).index_select(0, gidx)
                 states = [torch.cat([o_, n_], 1).index_select(1, gidx) for o_, n_ in zip(states, stepped)]
 
         # all hypotheses in one copy: per utterance the live-row count, lengths and tokens of ITS final buffer

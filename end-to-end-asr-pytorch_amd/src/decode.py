@@ -22,6 +22,7 @@ from .. import decoder_ops as dops
 from .. import gru_ops
 from .. import speller_ops as sops
 from .lm import RNNLM
+from .ngram import NGramLM, is_ngram_path
 from .ctc import CTCPrefixScore, LOG_ZERO
 
 CTC_BEAM_RATIO = 1.5   # (reference: src/decode.py:10)
@@ -49,14 +50,23 @@ class BeamDecoder(nn.Module):
         if self.apply_lm:
             self.lm_w = lm_weight
             self.lm_path = lm_path
-            lm_config = yaml.load(open(lm_config, 'r'), Loader=yaml.FullLoader)
-            self.lm = RNNLM(self.asr.vocab_size, **lm_config['model'])
-            self.lm.load_state_dict(torch.load(self.lm_path, map_location='cpu')['model'])
+            if is_ngram_path(lm_path):              # back-off n-gram (ARPA / saved image): lm_config is not read
+                self.lm = NGramLM.from_file(lm_path, self.asr.vocab_size)
+            else:
+                lm_config = yaml.load(open(lm_config, 'r'), Loader=yaml.FullLoader)
+                self.lm = RNNLM(self.asr.vocab_size, **lm_config['model'])
+                self.lm.load_state_dict(torch.load(self.lm_path, map_location='cpu')['model'])
             self.lm.eval()
 
         self.apply_emb = emb_decoder is not None
         if self.apply_emb:
             self.emb_decoder = emb_decoder
+
+    @property
+    def lm_logp_ready(self):
+        ''' an LM whose forward() already returns log-probabilities (the n-gram) is used as it is: a pruned back-off
+            model is not normalised and renormalising would change it '''
+        return self.apply_lm and getattr(self.lm, 'returns_logp', False)
 
     def create_msg(self):
         msg = ['Decode spec| Beam size = {}\t| Min/Max len ratio = {}/{}'.format(
@@ -66,6 +76,8 @@ class BeamDecoder(nn.Module):
         if self.apply_lm:
             msg.append('           |Joint LM decoding enabled \t| weight = {:.2f}\t| src = {}'.format(
                 self.lm_w, self.lm_path))
+            if isinstance(self.lm, NGramLM):
+                msg += self.lm.create_msg()
         if self.apply_emb:
             msg.append('           |Joint Emb. decoding enabled \t| weight = {:.2f}'.format(
                 self.emb_decoder.fuse_lambda.mean().cpu().item()))
@@ -213,7 +225,7 @@ class BeamDecoder(nn.Module):
             if self.apply_lm:
                 lm_out, lm_hid = self.lm(prev_token.unsqueeze(1), None, hidden=lm_hidden)
                 lm_h, lm_c = lm_hid if lm_lstm else (lm_hid, lm_hid)
-                lm_logp = ops.log_softmax(lm_out[:, 0, :])
+                lm_logp = lm_out[:, 0, :] if self.lm_logp_ready else ops.log_softmax(lm_out[:, 0, :])
             if self.apply_ctc or self.apply_lm:
                 cur_prob = dops.joint_score(att_logp, cand, psi, prev_ctc, lm_logp,
                                             self.ctc_w if self.apply_ctc else 0.0,
@@ -395,6 +407,9 @@ class BeamDecoder(nn.Module):
             return segs + [(lm_c[l], cs[l], lm_c.shape[2], 1, 0) for l in range(lm_c.shape[0])], (hs, cs)
 
         def lm_position(t, hid=None):
+            if self.lm_logp_ready:        # n-gram: the survivors' one-word states are read through `parent` in the launch
+                lm_out, lm_hid = self.lm(prev_token.unsqueeze(1), None, hidden=lm_h if t > 0 else None, parent=parent)
+                return lm_out[:, 0, :], lm_hid
             if t > 0 and hid is None:
                 segs, hid = lm_segments()
                 if len(segs) <= 8 and os.environ.get("ASRK_DECODE_MULTI_GATHER", "1") != "0":
@@ -437,7 +452,7 @@ class BeamDecoder(nn.Module):
                 if self.apply_ctc:
                     r_prev = torch.empty((R, Te, 2), **f32)
                     segs.append((r_new, r_prev, 2 * Te, C, 1))
-                if self.apply_lm and lm_side is None:
+                if self.apply_lm and lm_side is None and not self.lm_logp_ready:
                     lsegs, hid = lm_segments()
                     if len(segs) + len(lsegs) <= 8:
                         segs += lsegs

@@ -398,6 +398,33 @@ int asrk_ctc_prefix_beam_multi_f32(const float *ctc, int64_t ctc_row_stride, int
                                    const int *frames, const int *t_start, int j, int *out_parent, int *out_last,
                                    int *out_gidx, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- back-off n-gram LM step for shallow fusion (no counterpart in the reference, which fuses an RNN-LM only) ----
+ * One decode position of an ARPA back-off model for R rows: row r continues the state state_in[parent ? parent[r] : r]
+ * (state_in == NULL: the empty context), consumes token[r], writes its new state (one int32: a context node) to
+ * state_out[r] and ln p(v | new context) for every v to out[r * row_stride + v], v < V (columns V .. row_stride - 1
+ * are not touched).  One workgroup per row, the row written in place (no staging, no limit on V).
+ *   image (device memory, built by src/ngram.py: build_image; node 0 = the empty context):
+ *     uni_logp [V] f32, uni_next [V] int32: the unigram level, dense - ln(10) * -99 and state 0 for a word without
+ *       a unigram; bo [n_nodes] f32, fail [n_nodes] int32 (the context without its oldest token, fail[0] = 0),
+ *       child_off [n_nodes + 1] int32 (CSR; node 0 has no entries); word (ascending inside a node), logp, next
+ *       [n_entries]: the explicit n-grams above the unigram level, next = the state after the word (resolved by the
+ *       builder, for top-order entries too).  word / logp / next may be NULL when n_entries == 0 (a unigram model).
+ *   advance: binary-search token[r] among the children of the state, follow fail on a miss, uni_next at node 0; a
+ *       token outside [0, V) leads to the empty context.
+ *   scores: with the chain c_0 = new state, c_k = fail[c_k-1], c_d = 0 and B_0 = +0, B_k = fl(B_k-1 + bo[c_k-1]):
+ *       out[v] = fl(B_d + uni_logp[v]), then for k = d - 1 .. 0 out[word[e]] = fl(B_k + logp[e]) over the entries of
+ *       c_k (the longest context wins).  f32 adds in exactly this order, no atomics: a row's result depends on the
+ *       image and its own (state, token) only, not on R, its position or the launch.
+ *   token [R] int64; parent [R] int32, or int64 when parent_is_i64 != 0, or NULL; n_state = rows of state_in (a
+ *       parent outside [0, n_state) reads the empty context); state_out must not be state_in.
+ * ASRK_EINVAL, checked before any device call: order outside 1..8, V <= 0, n_nodes < 1, a negative count, a NULL
+ * image array, row_stride < V; for R > 0 also a NULL token / state_out / out.  R == 0 is ASRK_OK. */
+int asrk_ngram_step_f32(int order, int V, int n_nodes, int n_entries, const float *uni_logp,
+                        const int32_t *uni_next, const float *bo, const int32_t *fail, const int32_t *child_off,
+                        const int32_t *word, const float *logp, const int32_t *next, const int32_t *state_in,
+                        int n_state, const int64_t *token, const void *parent, int parent_is_i64, int32_t *state_out,
+                        float *out, int64_t row_stride, int R, void *stream);
+
 /* ---- attention decoder step (src/module.py:179-258, src/asr.py:277-313) -------------------
  * BN = B*num_head rows ordered (b, head).  All tensors contiguous f32; lens int64 [B].
  * loc_conv:  c[b,t,k] = sum_{n,j} prev_att[b,n,t+j-ks] * Wc[k,n,j]   (Conv1d(N,K,2ks+1,pad ks))
