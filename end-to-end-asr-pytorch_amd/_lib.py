@@ -123,6 +123,8 @@ SIGNATURES = {
     "asrk_attn_energy_bwd_f32": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                          c_int, c_f32, c_vp]),
+    "asrk_attn_energy_plan": (c_int, [c_int] * 6 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                                    ctypes.POINTER(c_i64)]),
     "asrk_attn_context_fwd_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_vp]),
     "asrk_attn_context_bwd_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_vp]),
     "asrk_lstm_cell_fwd_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),

@@ -431,6 +431,52 @@ static inline int energy_tpb(int BN, int T) {
     return asrk_div_up(T, tc);
 }
 
+// The launch geometry of energy_fwd_kernel / energy_bwd_kernel: the one place that knows tpb and the two LDS layouts.
+// K is the launch's own (0 for dot energies).  ASRK_ESHAPE when the shape does not fit (the backward first halves tpb
+// down to 8: its per-wave dWp partials dominate LDS, tpb only adds tpb*K).
+struct EnergyPlan {
+    int tpb, chunks;   // frames per workgroup, workgroups per (batch, head) row
+    size_t lds;
+};
+
+static int energy_plan(bool loc, bool bwd, int BN, int T, int A, int K, EnergyPlan *p) {
+    int tpb = energy_tpb(BN, T);
+    size_t lds = 0;
+    if (!bwd) {
+        lds = (size_t)(A + (loc ? A + A * K + tpb * K : 0)) * sizeof(float);
+    } else {
+        for (;;) {
+            lds = (size_t)(A + 4 * A + (loc ? A + 4 * A + A * K + tpb * K + 4 * A * K : 0)) * sizeof(float);
+            if (lds <= 150 * 1024 || tpb <= 8) break;
+            tpb = (tpb + 1) / 2;
+        }
+    }
+    if (lds > 150 * 1024) return ASRK_ESHAPE;
+    p->tpb = tpb;
+    p->chunks = asrk_div_up(T, tpb);
+    p->lds = lds;
+    return ASRK_OK;
+}
+
+extern "C" int asrk_attn_energy_plan(int loc, int bwd, int BN, int T, int A, int K, int *tpb, int *chunks,
+                                     int64_t *lds_bytes) {
+    if (tpb) *tpb = 0;
+    if (chunks) *chunks = 0;
+    if (lds_bytes) *lds_bytes = 0;
+    if (!tpb || !chunks || !lds_bytes) return ASRK_EINVAL;
+    if (BN < 0 || T <= 0 || A <= 0) return ASRK_EINVAL;
+    if (BN == 0) return ASRK_OK;
+    if (loc && bwd && K > 16) return ASRK_ESHAPE;
+    if (loc && K <= 0) return ASRK_EINVAL;
+    EnergyPlan p;
+    const int rc = energy_plan(loc != 0, bwd != 0, BN, T, A, loc ? K : 0, &p);
+    if (rc != ASRK_OK) return rc;
+    *tpb = p.tpb;
+    *chunks = p.chunks;
+    *lds_bytes = (int64_t)p.lds;
+    return ASRK_OK;
+}
+
 extern "C" int asrk_attn_energy_fwd_f32(int loc, const float *key, const float *q, const float *c,
                                         const float *Wp, const float *we, const float *be,
                                         const int64_t *lens, float *attn, float *e_scratch, int B,
@@ -440,11 +486,11 @@ extern "C" int asrk_attn_energy_fwd_f32(int loc, const float *key, const float *
     if (!key || !q || !lens || !attn || !e_scratch) return ASRK_EINVAL;
     if (loc && (!c || !Wp || !we || !be || K <= 0)) return ASRK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int tpb = energy_tpb(B * N, T);
-    EnergyArgs a{key, q, c, Wp, we, be, lens, e_scratch, N, T, A, loc ? K : 0, tpb, 1.f / temperature};
-    const size_t lds = (size_t)(A + (loc ? A + A * K + tpb * K : 0)) * sizeof(float);
-    if (lds > 150 * 1024) return ASRK_ESHAPE;
-    const dim3 grid(B * N, asrk_div_up(T, tpb));
+    EnergyPlan pl;
+    if (energy_plan(loc != 0, false, B * N, T, A, loc ? K : 0, &pl) != ASRK_OK) return ASRK_ESHAPE;
+    const size_t lds = pl.lds;
+    EnergyArgs a{key, q, c, Wp, we, be, lens, e_scratch, N, T, A, loc ? K : 0, pl.tpb, 1.f / temperature};
+    const dim3 grid(B * N, pl.chunks);
     asrk_prof_begin_(PROF_ATTN, s);
     if (loc) {
         ASRK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(energy_fwd_kernel<true>),
@@ -474,17 +520,12 @@ extern "C" int asrk_attn_energy_bwd_f32(int loc, const float *key, const float *
     if (loc && (!c || !Wp || !we || !dc || !dWp_acc || !dwe_acc || !dbe_acc || K <= 0))
         return ASRK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    int tpb = energy_tpb(B * N, T);
-    size_t lds = 0;
-    for (;;) {  // shrink-proof: the per-wave dWp partials dominate LDS, tpb only adds tpb*K
-        lds = (size_t)(A + 4 * A + (loc ? A + 4 * A + A * K + tpb * K + 4 * A * K : 0)) * sizeof(float);
-        if (lds <= 150 * 1024 || tpb <= 8) break;
-        tpb = (tpb + 1) / 2;
-    }
-    if (lds > 150 * 1024) return ASRK_ESHAPE;
+    EnergyPlan pl;
+    if (energy_plan(loc != 0, true, B * N, T, A, loc ? K : 0, &pl) != ASRK_OK) return ASRK_ESHAPE;
+    const size_t lds = pl.lds;
     EnergyBwdArgs a{key, q, c, Wp, we, lens, attn, dattn, dkey_acc, dq, dc, dWp_acc, dwe_acc, dbe_acc,
-                    N, T, A, loc ? K : 0, tpb, 1.f / temperature};
-    const dim3 grid(B * N, asrk_div_up(T, tpb));
+                    N, T, A, loc ? K : 0, pl.tpb, 1.f / temperature};
+    const dim3 grid(B * N, pl.chunks);
     asrk_prof_begin_(PROF_ATTN, s);
     ASRK_HIP(hipMemsetAsync(dq, 0, (size_t)B * N * A * sizeof(float), s));
     if (loc) {

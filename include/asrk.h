@@ -450,6 +450,16 @@ int asrk_attn_energy_bwd_f32(int loc, const float *key, const float *q, const fl
                              const float *attn, const float *dattn, float *dkey_acc, float *dq,
                              float *dc, float *dWp_acc, float *dwe_acc, float *dbe_acc, int B,
                              int N, int T, int A, int K, float temperature, void *stream);
+/* The launch geometry asrk_attn_energy_fwd_f32 (bwd == 0) / asrk_attn_energy_bwd_f32 (bwd != 0) use for BN = B*N rows,
+ * from the one host function both launchers call; host only (no device call, runs without a GPU;
+ * tests/test_attention_plan_cpu.py holds the attention case table to it).  K is ignored when loc == 0.
+ *   *tpb: frames per workgroup (the backward halves it, down to 8, while its LDS exceeds 150 KB)
+ *   *chunks: workgroups per row = ceil(T / tpb) (grid = BN x chunks)   *lds_bytes: dynamic LDS of the launch
+ * The status is the launcher's for the same sizes: ASRK_EINVAL for BN < 0, T <= 0, A <= 0, loc with K <= 0 (or a NULL
+ * output pointer here); ASRK_ESHAPE for loc && bwd && K > 16 and for LDS over 150 KB; BN == 0 is ASRK_OK.  The three
+ * outputs are 0 unless a launch would happen. */
+int asrk_attn_energy_plan(int loc, int bwd, int BN, int T, int A, int K, int *tpb, int *chunks,
+                          int64_t *lds_bytes);
 int asrk_attn_context_fwd_f32(const float *attn, const float *value, float *ctx, int BN, int T,
                               int Dv, int64_t ctx_stride, void *stream);
 int asrk_attn_context_bwd_f32(const float *dctx, const float *value, float *dattn, int BN, int T,
