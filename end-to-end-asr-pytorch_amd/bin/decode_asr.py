@@ -15,11 +15,18 @@ wrapped so that it is called with it; without the block nothing here changes.
 
 The optional key `decode: {align: true}` turns the run into CTC forced alignment of both sets to their reference
 transcripts instead of decoding (bin/align_asr.py); without the key nothing here changes.
+
+The optional block `decode: {rescore: {enable: true, first_pass_lm: false, workspace_mb: 1024}}` selects two-pass
+decoding (src/rescore.py): a CTC prefix beam search, then attention (+LM) rescoring of its n-best list.  The block
+never reaches the other decoders; besides the usual two files (the beam file in rescored order) a third one,
+`..._rescore-<beam>-<ctc_weight>-<lm_weight>.csv`, lists every hypothesis with its scores.  Without the block nothing
+here changes.
 """
 import os
 
 from . import align_asr, test_asr
 from ..parallel import gather_in_order
+from ..src.rescore import RescoreDecoder, check_decode_config
 
 
 class _FusedGreedy:
@@ -37,6 +44,10 @@ class Solver(test_asr.Solver):
 
     def __init__(self, config, paras, mode):
         self.align = bool(config['decode'].get('align', False))
+        check_decode_config(config['decode'], config.get('emb'))
+        # taken out of the block: the parent hands the whole decode block to BeamDecoder(**dcfg)
+        rescore = config['decode'].pop('rescore', None) or {}
+        self.rescore = dict(rescore) if rescore.get('enable', False) else None
         if self.align:
             # the search settings are not used, but the parent reads beam_size: 1 makes it take its greedy set-up
             # (batch size of the training config) ...
@@ -48,6 +59,21 @@ class Solver(test_asr.Solver):
             self.config['data']['corpus']['batch_size'] = 1
 
     def set_model(self):
+        if getattr(self, 'rescore', None):
+            init_adadelta = self.config['hparas']['optimizer'] == 'Adadelta'
+            self.model = test_asr.ASR(self.feat_dim, self.vocab_size, init_adadelta,
+                                      **self.config['model']).to(self.device)
+            self.load_ckpt()        # eval mode
+            dcfg = self.config['decode']
+            self.decoder = RescoreDecoder(self.model, dcfg['beam_size'], dcfg['vocab_candidate'],
+                                          ctc_weight=dcfg.get('ctc_weight', 0.0), lm_path=dcfg.get('lm_path', ''),
+                                          lm_config=dcfg.get('lm_config', ''), lm_weight=dcfg.get('lm_weight', 0.0),
+                                          first_pass_lm=self.rescore.get('first_pass_lm', False),
+                                          workspace_mb=self.rescore.get('workspace_mb', 1024), device=self.device)
+            self.ctc_only = False
+            self.enable_att = self.model.enable_att
+            self.verbose(self.decoder.create_msg())
+            return
         if not getattr(self, 'align', False):
             super().set_model()
             if self.greedy and self.emb_decoder is not None:
@@ -72,6 +98,8 @@ class Solver(test_asr.Solver):
     def exec(self):
         if getattr(self, 'align', False):      # (a solver assembled without __init__ decodes)
             return align_asr.run(self)
+        if getattr(self, 'rescore', None):
+            return self.exec_rescore()
         group = max(1, int(os.environ.get('ASRK_DECODE_BATCH', '16')))
         if self.greedy or not self.ctc_only or not self.decoder.apply_lm or group == 1:
             return super().exec()
@@ -103,3 +131,54 @@ class Solver(test_asr.Solver):
             self.verbose('Results/Beams will be stored at {} / {}.'.format(self.cur_output_path, self.cur_beam_path))
             self.write_hyp(results, self.cur_output_path, self.cur_beam_path)
         self.verbose('All done !')
+
+    def exec_rescore(self):
+        ''' two-pass decoding: the parent's beam branch with RescoreDecoder.forward_batch per group, plus the score file '''
+        dcfg = self.config['decode']
+        group = max(1, int(os.environ.get('ASRK_DECODE_BATCH', '16')))
+        for s, ds in zip(['dev', 'test'], [self.dv_set, self.tt_set]):
+            self.cur_output_path = self.output_file.format(s, 'output')
+            self.cur_beam_path = self.output_file.format(
+                s, 'beam-{}-{}'.format(dcfg['beam_size'], dcfg.get('lm_weight', 0.0)))
+            score_path = self.output_file.format(s, 'rescore-{}-{}-{}'.format(
+                dcfg['beam_size'], dcfg.get('ctc_weight', 0.0), dcfg.get('lm_weight', 0.0)))
+            if self.rank == 0:
+                with open(self.cur_output_path, 'w', encoding='UTF-8') as f:
+                    f.write('idx\thyp\ttruth\n')
+                with open(self.cur_beam_path, 'w') as f:
+                    f.write('idx\tbeam\thyp\ttruth\n')
+                with open(score_path, 'w', encoding='UTF-8') as f:
+                    f.write('idx\trank\tfirst_rank\tscore\tctc\tatt\tlm\thyp\ttruth\n')
+            self.verbose('Performing CTC n-best rescoring on {} set, num of batch = {}.'.format(s, len(ds)))
+            mine, ids, n_utt = self._my_share(ds)
+            local, pending = [], []
+            for k, data in enumerate(mine):
+                self.progress('Decode - {}/{}'.format(ids[k] + 1, n_utt))
+                pending.append(data)
+                if len(pending) == group:
+                    local += rescore_decode_many(pending, self.decoder, self.device)
+                    pending = []
+            if pending:
+                local += rescore_decode_many(pending, self.decoder, self.device)
+            results = gather_in_order(local, n_utt, self.dist, self.rank, self.world)
+            if results is None:          # not rank 0: its rows have been handed over
+                continue
+            self.verbose('Results/Beams/Scores will be stored at {} / {} / {}.'.format(
+                self.cur_output_path, self.cur_beam_path, score_path))
+            self.write_hyp([(name, [list(h[0]) for h in hyps], truth) for name, hyps, truth in results],
+                           self.cur_output_path, self.cur_beam_path)
+            with open(score_path, 'a', encoding='UTF-8') as f:
+                for name, hyps, truth in results:
+                    ref = self.tokenizer.decode(truth)
+                    for b, h in enumerate(hyps):
+                        tokens, score, ctc, att, lm, first_rank = h
+                        f.write('\t'.join([name, str(b), str(first_rank), repr(score), repr(ctc), repr(att), repr(lm),
+                                           self.tokenizer.decode(list(tokens)), ref]) + '\n')
+        self.verbose('All done !')
+
+
+def rescore_decode_many(items, model, device):
+    ''' several batch-1 loader items -> (name, [(tokens, score, ctc, att, lm, first_rank)] best first, truth) rows '''
+    feat, lens = test_asr._pad_items(items, device)
+    hyps = model.forward_batch(feat, lens)
+    return [(d[0][0], [tuple(h) for h in hyps[u]], d[3][0].cpu().tolist()) for u, d in enumerate(items)]

@@ -1422,6 +1422,79 @@ def ctc_align(log_probs, targets, input_lengths, target_lengths, blank=0, flags=
     return CTCAlignment(states, tokens, spans, score)
 
 
+# --------------------------------------------------------------------------- second-pass scoring (inference only)
+SEQ_LOGP_NORMALIZED = 1      # ASRK_SEQ_LOGP_NORMALIZED (include/asrk.h)
+
+
+@torch.no_grad()
+def seq_logp(x, target, seg_off=None, normalized=False):
+    """Log-probability of target[m] under row m of the logits x [M, V] (asrk_seq_logp_f32: no [M, V] log_softmax is
+    written) -> (tok_logp f32 [M], seq_logp f64 [R] or None).  A row with target < 0 is skipped (0, never read);
+    target >= V gives NaN.  `seg_off` [R+1]: seq_logp[r] = the float64 sum of tok_logp[seg_off[r]:seg_off[r+1]], added
+    in ascending order.  `normalized`: x already holds log-probabilities, the value is gathered as it is.  x may be
+    a row-strided view (stride(1) == 1)."""
+    _require_gpu(x)
+    L = _L()
+    if x.dim() != 2:
+        raise _lib.AsrkError("seq_logp: x must be [M, V]")
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    M, V = x.shape
+    dev = x.device
+    ldx = x.stride(0) if M > 1 else max(x.stride(0), V)
+    target = torch.as_tensor(target).to(device=dev, dtype=torch.int64).contiguous()
+    if target.numel() != M:
+        raise _lib.AsrkError("seq_logp: one target per row of x")
+    tok = torch.empty((M,), dtype=torch.float32, device=dev)
+    seq, R = None, 0
+    if seg_off is not None:
+        seg_off = torch.as_tensor(seg_off).to(device=dev, dtype=torch.int64).contiguous()
+        if seg_off.dim() != 1 or seg_off.numel() < 1:
+            raise _lib.AsrkError("seq_logp: seg_off must be [R + 1]")
+        R = seg_off.numel() - 1
+        seq = torch.empty((R,), dtype=torch.float64, device=dev)
+    _lib.check(L.asrk_seq_logp_f32(_p(x), ldx, _p(target), _p(seg_off), M, V, R,
+                                   SEQ_LOGP_NORMALIZED if normalized else 0, _p(tok), _p(seq), _stream()), "seq_logp")
+    return tok, seq
+
+
+@torch.no_grad()
+def ctc_score_rows(lp, mem_len, row_mem, targets, tgt_len, blank=0):
+    """log p_ctc of R hypotheses against the posteriors of U utterances (asrk_ctc_score_rows_f32): lp [U, Tmax, V]
+    log-probabilities, mem_len [U] frames of every utterance (frames beyond are never read), row r scores
+    targets[r, :tgt_len[r]] against utterance row_mem[r] -> score f32 [R] (-inf: no path; NaN: a label or a row_mem out
+    of range)."""
+    _require_gpu(lp)
+    L = _L()
+    if lp.dim() != 3:
+        raise _lib.AsrkError("ctc_score_rows: lp must be [U, Tmax, V]")
+    if lp.dtype != torch.float32:
+        lp = lp.float()
+    if lp.stride(2) != 1:
+        lp = lp.contiguous()
+    U, Tmax, V = lp.shape
+    dev = lp.device
+    targets = torch.as_tensor(targets).to(device=dev, dtype=torch.int64)
+    if targets.dim() != 2:
+        raise _lib.AsrkError("ctc_score_rows: only padded 2-D targets [R, L] are supported")
+    targets = targets.contiguous()
+    ml = torch.as_tensor(mem_len).to(device=dev, dtype=torch.int64).contiguous()
+    rm = torch.as_tensor(row_mem).to(device=dev, dtype=torch.int64).contiguous()
+    tl = torch.as_tensor(tgt_len).to(device=dev, dtype=torch.int64).contiguous()
+    R, Lmax = targets.shape
+    if ml.numel() != U or rm.numel() != R or tl.numel() != R:
+        raise _lib.AsrkError("ctc_score_rows: lengths / row_mem do not match lp and targets")
+    score = torch.empty((R,), dtype=torch.float32, device=dev)
+    need = L.asrk_ctc_score_rows_ws_bytes(R, Tmax, Lmax)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+    _lib.check(L.asrk_ctc_score_rows_f32(_p(lp), lp.stride(0), lp.stride(1), U, Tmax, V, _p(ml), _p(rm), _p(targets),
+                                         max(targets.stride(0), Lmax), Lmax, _p(tl), R, blank, _p(score), _p(ws), need,
+                                         _stream()), "ctc_score_rows")
+    return score
+
+
 # --------------------------------------------------------------------------- cross entropy
 def _check_label_smoothing(eps):
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:

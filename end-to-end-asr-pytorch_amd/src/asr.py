@@ -14,6 +14,9 @@ from .module import (VGGExtractor, CNNExtractor, RNNLayer, RNNParams, ScaleDotAt
                      LocationAwareAttention)
 
 
+SCORE_BLOCK = 16     # hypotheses per launch group of ASR.score_hypotheses (fixed: see there)
+
+
 class ASR(nn.Module):
     ''' ASR model, including Encoder/Decoder(s) (reference: src/asr.py:12-155) '''
 
@@ -249,6 +252,96 @@ class ASR(nn.Module):
         x = ops.dropout(states, dec.dropout, self.training)       # Decoder.final_dropout (src/asr.py:220)
         att_output = ops.linear(x, dec.char_trans.weight, dec.char_trans.bias)
         return att_output, att_seq, states
+
+    @torch.no_grad()
+    def score_hypotheses(self, encode_feature, encode_len, row_mem, ids, lens, workspace_mb=1024):
+        ''' Attention-decoder log-probabilities of R given token sequences (second-pass rescoring), teacher-forced in
+            eval mode - the arithmetic of forward(..., tf_rate=1, teacher=ids).  encode_feature [U,T',D] / encode_len
+            [U]: the encoder's output; row r is scored against utterance row_mem[r]; ids [R,L] int64: the hypotheses
+            with <eos> appended, zero-padded; lens [R]: their lengths, <eos> included.
+            -> (tok_logp f32 [R,L]: log softmax(att_logits_t)[ids[r,t]], 0 on padding; s_att f64 [R]: their sums).
+            The attention's key / value projections are built once per utterance and gathered per row; the loop is the
+            fused teacher-forced loop where forward() would take it (sops.supported_train_loop), else forward()'s
+            step-by-step loop on the gathered encoder rows.  The vocabulary logits exist for one chunk of whole
+            hypotheses at a time (repeated memory + logits of a chunk stay below workspace_mb) and are reduced by
+            ops.seq_logp.  Rows go through in blocks of SCORE_BLOCK whatever the workspace is, so chunking changes no
+            value. '''
+        if not self.enable_att:
+            raise RuntimeError('ASR.score_hypotheses needs the attention decoder: this model has ctc_weight = 1')
+        if self.training:
+            raise RuntimeError('ASR.score_hypotheses scores in eval mode: call model.eval() first')
+        att, dec, al = self.attention, self.decoder, self.attention.att_layer
+        dev = encode_feature.device
+        ids = torch.as_tensor(ids).to(device=dev, dtype=torch.int64)
+        R, L = ids.shape
+        tok_all = torch.zeros((R, L), dtype=torch.float32, device=dev)
+        seq_all = torch.zeros((R,), dtype=torch.float64, device=dev)
+        if R == 0 or L == 0:
+            return tok_all, seq_all
+        lens = torch.as_tensor(lens).to(device=dev, dtype=torch.int64)
+        row_mem = torch.as_tensor(row_mem).to(device=dev, dtype=torch.int64)
+        enc_len = encode_len.to(dev)
+        target = torch.where(torch.arange(L, device=dev).unsqueeze(0) < lens.unsqueeze(1), ids,
+                             torch.full_like(ids, -1))
+        T = encode_feature.shape[1]
+        W = self.pre_embed.weight
+        fused = sops.supported_train_loop(att, dec, False)
+        att.reset_mem()
+        if fused:
+            key, value = self._speller_memory(encode_feature, encode_len)
+            mem_floats = T * (key.shape[2] + value.shape[2])
+        else:
+            mem_floats = T * (encode_feature.shape[2] + att.num_head * (att.dim + att.v_dim))
+        # Every launch sees exactly SCORE_BLOCK rows (the last block is filled up with copies of its first row): GEMM
+        # and step kernels pick their variant by the row count, so a launch shape that followed the chunk size would
+        # let workspace_mb change low-order bits.  A chunk is a whole number of blocks; it decides only how much
+        # repeated memory exists at a time.
+        B = SCORE_BLOCK
+        Rp = -(-R // B) * B
+        if Rp > R:
+            fill = (torch.arange(R, Rp, device=dev) // B) * B          # the first row of the block a filler sits in
+            row_mem, ids = torch.cat([row_mem, row_mem[fill]]), torch.cat([ids, ids[fill]])
+            target = torch.cat([target, target[fill]])
+            tok_all = torch.zeros((Rp, L), dtype=torch.float32, device=dev)
+            seq_all = torch.zeros((Rp,), dtype=torch.float64, device=dev)
+        per_row = 4 * (2 * mem_floats + L * (self.vocab_size + 2 * dec.dim * dec.layer))
+        chunk = max(1, int(workspace_mb * 2 ** 20) // (per_row * B)) * B
+        sos_emb = dops.embedding(torch.zeros((B,), dtype=torch.long, device=dev), W)
+        seg = torch.arange(B + 1, dtype=torch.int64, device=dev) * L
+        self.score_chunks = -(-Rp // chunk)       # how many chunks the last call took (tools / tests read it)
+        for c0 in range(0, Rp, chunk):
+            rows = row_mem[c0:c0 + chunk]
+            len_chunk = enc_len.index_select(0, rows)
+            if fused:
+                key_chunk, value_chunk = key.index_select(0, rows), value.index_select(0, rows)
+            else:
+                feat_chunk = encode_feature.index_select(0, rows)
+            for b0 in range(0, rows.numel(), B):
+                r0 = c0 + b0
+                len_rows = len_chunk[b0:b0 + B]
+                teacher = dops.embedding(ids[r0:r0 + B].contiguous(), W)
+                att.reset_mem()
+                if fused:
+                    key_rows, value_rows = key_chunk[b0:b0 + B], value_chunk[b0:b0 + B]
+                    al.compute_mask(key_rows, len_rows)
+                    logits, _, _ = self._teacher_forced_loop(key_rows, len_rows, sos_emb, teacher, L,
+                                                             memory=(key_rows, value_rows))
+                else:
+                    feat_rows = feat_chunk[b0:b0 + B]
+                    dec.init_state(B)
+                    last_char, state_seq = sos_emb, []
+                    for t in range(L):
+                        _, context = att(dec.get_query(), feat_rows, len_rows)
+                        _, d_state = dec(dops.concat_last(last_char, context), project=False)
+                        last_char = teacher[:, t, :]
+                        state_seq.append(d_state)
+                    states = dops.stack_steps(state_seq)                                  # [B,L,D]
+                    logits = ops.linear(states, dec.char_trans.weight, dec.char_trans.bias)
+                tok, seq = ops.seq_logp(logits.reshape(B * L, self.vocab_size), target[r0:r0 + B].reshape(-1), seg)
+                tok_all[r0:r0 + B] = tok.view(B, L)
+                seq_all[r0:r0 + B] = seq
+        att.reset_mem()
+        return tok_all[:R], seq_all[:R]
 
     def _greedy_loop(self, encode_feature, encode_len, sos_emb, decode_step):
         ''' argmax-feedback decoding without autograd -> (att_output [B,L,V], att_seq [B,1,L,T], states) '''

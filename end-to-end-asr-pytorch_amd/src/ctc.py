@@ -406,6 +406,14 @@ class CTCBeamDecoder(nn.Module):
         ctc = ops.log_softmax(ops.linear(enc, asr.ctc_layer.weight, asr.ctc_layer.bias))
         ctc = ops.log_softmax(ctc)               # the reference re-applies log_softmax (forward() below)
         enc_len_h = [int(v) for v in asr.encoder.packed_frames.cpu().tolist()]   # forward() searches the whole tensor
+        return self.search_batch(ctc, enc_len_h, n_streams)
+
+    @torch.no_grad()
+    def search_batch(self, ctc, enc_len_h, n_streams=16):
+        ''' the searches of forward_batch on posteriors that already exist: ctc [U,T',V] (log_softmax applied twice, as
+            forward() searches them), enc_len_h: U frame counts on the host -> U hypothesis lists '''
+        U = ctc.shape[0]
+        dev = ctc.device
         if self.apply_lm:
             return self.search_device_batch(ctc, enc_len_h)
         amax = ops.argmax(ctc).cpu().numpy()                                     # [U, T']

@@ -1128,6 +1128,43 @@ int asrk_ctc_align_f32(const float *lp, int64_t stride_t, int64_t stride_b, int 
                        const int64_t *target_lengths, int blank, int flags, int32_t *states, int32_t *tokens,
                        int32_t *spans, float *score, int64_t *stamps, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- second-pass scoring (n-best rescoring; csrc/rescore.hip).  Inference only: no gradients. ---------------------
+ * Token and sequence log-probabilities from logits, without a [M,V] log_softmax tensor:
+ *   x [M,V] f32, row stride ldx >= V; target [M] int64;
+ *   tok_logp[m] = x[m, target[m]] - logsumexp(x[m, :])  (one pass over the row: running max and sum per lane,
+ *   max-subtracted, f32), or x[m, target[m]] alone with ASRK_SEQ_LOGP_NORMALIZED (x already holds log-probabilities).
+ *   target[m] < 0: the row is skipped - tok_logp[m] = 0 and the row is never read; target[m] >= V: NaN, nothing read.
+ *   seq_logp[r] (float64, r < R) = sum of (double)tok_logp[m] for m in [seg_off[r], seg_off[r+1]) (seg_off [R+1] int64,
+ *   clipped to [0, M]), added one after the other in ascending m: reproducible bit for bit; an empty segment gives 0.
+ *   seg_off and seq_logp may both be NULL (no sums; R is ignored then).
+ * Rows shorter than 2048 take one wave each (4 rows per workgroup), longer ones a 256-thread workgroup each; loads are
+ * 16 bytes wide when x is 16-byte aligned and ldx % 4 == 0, scalar otherwise.  No float atomics.
+ * ASRK_EINVAL, before any device call: a NULL pointer with M > 0, only one of seg_off / seq_logp, a negative size,
+ * V <= 0, ldx < V, unknown flags.  M == 0 (and R == 0) is ASRK_OK without a launch. */
+#define ASRK_SEQ_LOGP_NORMALIZED 1
+int asrk_seq_logp_f32(const float *x, int64_t ldx, const int64_t *target, const int64_t *seg_off, int M, int V, int R,
+                      int flags, float *tok_logp, double *seq_logp, void *stream);
+
+/* CTC log-likelihood of R hypotheses against the posteriors of U utterances (usually U < R): row r scores
+ * targets[r, :tgt_len[r]] against the mem_len[row_mem[r]] frames of utterance row_mem[r]; frame t of utterance u at
+ * lp + u*stride_u + t*stride_t (log-probabilities, V per frame).  mem_len [U], row_mem [R], tgt_len [R], targets
+ * [R, tgt_stride] are int64 device arrays; row_mem need not be sorted; frames >= mem_len[u] are never read (lengths are
+ * clipped to [0, Tmax] and [0, Lmax]).
+ *   score[r] = log p_ctc: -inf when the target does not fit the frames (or there is no frame and tgt_len > 0), the sum
+ *   of the blank log-probabilities for tgt_len == 0 (0 without frames), NaN for a label outside [0,V) or a row_mem
+ *   outside [0,U) - neither reads out of bounds.
+ * Alpha only, one wave per row, no lattice is stored; the arithmetic is asrk_ctc_loss_fwd_f32's (hardware exp/log for
+ * 2*Lmax+1 <= 256 and Tmax <= 512, the library functions beyond), so score[r] = -nll of the same row.
+ * ws: caller-owned device memory, 16-byte aligned, at least asrk_ctc_score_rows_ws_bytes(R, Tmax, Lmax) bytes (the
+ * gathered log-probs [R, Tmax, 2*Lmax+1]); the size function returns 0 for arguments without work or that the call
+ * rejects.  ASRK_EINVAL, before any device call: a NULL pointer, a negative size or stride, tgt_stride < Lmax, blank
+ * outside [0,V), a NULL / misaligned / short workspace; ASRK_ESHAPE: 2*Lmax+1 > 2048.  R == 0 is ASRK_OK. */
+size_t asrk_ctc_score_rows_ws_bytes(int R, int Tmax, int Lmax);
+int asrk_ctc_score_rows_f32(const float *lp, int64_t stride_u, int64_t stride_t, int U, int Tmax, int V,
+                            const int64_t *mem_len, const int64_t *row_mem, const int64_t *targets, int64_t tgt_stride,
+                            int Lmax, const int64_t *tgt_len, int R, int blank, float *score, void *ws, size_t ws_bytes,
+                            void *stream);
+
 /* ---- CTC prefix scores for joint CTC-attention beam search (src/ctc.py:76-116) -----------
  * All (hypothesis h, candidate c) pairs of one beam step in one launch.  x [T,V] log-probs;
  * r_prev [n,T,2] (0 = non-blank, 1 = blank path) of each hypothesis' prefix g_h; prefix_len[h] =
