@@ -220,6 +220,9 @@ SIGNATURES = {
     "asrk_ctc_align_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_int,
                                    c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "asrk_seq_logp_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "asrk_seq_logp_lse_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_seq_logp_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
+    "asrk_mwer_loss_f64": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "asrk_ctc_score_rows_ws_bytes": (c_sz, [c_int, c_int, c_int]),
     "asrk_ctc_score_rows_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
                                         c_int, c_int, c_vp, c_vp, c_sz, c_vp]),

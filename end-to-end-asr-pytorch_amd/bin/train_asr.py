@@ -15,6 +15,7 @@ from ..src.optim import Optimizer
 from ..src.data import load_dataset
 from ..src.audio import SpecAugment, SpeedPerturb, Dither, NoiseReverb
 from ..src.loss import LossOptions
+from ..src.mwer import MWEROptions, MWERLoss
 from ..src.util import human_format, cal_er
 
 
@@ -102,6 +103,12 @@ class Solver(BaseSolver):
             self.verbose(self.emb_decoder.create_msg())
         self.optimizer = Optimizer(model_paras, **self.config['hparas'])
         self.verbose(self.optimizer.create_msg())
+        # MWER fine-tuning (top-level `mwer:` block; None = the step is exactly what it was)
+        self.mwer = None
+        mwer_opts = MWEROptions.from_config(self.config)
+        if mwer_opts is not None:
+            self.mwer = MWERLoss(self.model, self.tokenizer, mwer_opts)
+            self.verbose(self.mwer.create_msg())
         self.load_ckpt()
         self.enable_data_parallel()
 
@@ -121,6 +128,7 @@ class Solver(BaseSolver):
             counts = torch.stack([txt_len.new_tensor(txt.shape[0]), txt_len.sum()]).to(torch.float64)
             w = (counts / self.dp.count_normaliser(counts)).to(torch.float32)
             w_ctc, w_att = w[0], w[1]
+        self.w_utt = w_ctc          # the utterance-count weight of this step (MWER is a mean over utterances too)
         if emb_loss is not None:
             shown_loss = shown_loss + emb_loss.detach() * self.emb_decoder.weight
             total_loss += emb_loss * self.emb_decoder.weight
@@ -169,12 +177,30 @@ class Solver(BaseSolver):
                     feat = self.specaug(feat, data[2], self.paras.seed, self.step, self.rank, feat_len_dev=feat_len)
                 self.timer.cnt('rd')
 
+                # MWER step: the n-best lists of this batch first (the search runs its own eval-mode encoder pass)
+                mwer_on = self.mwer is not None and self.step >= self.mwer.opts.start_step
+                nbest = self.mwer.nbest(feat, feat_len) if mwer_on else None
+                # the MWER step runs the encoder itself: the hypotheses are scored on the very output the training
+                # forward decodes from (ASR.forward(encoded=...): the same call it would make, so the same launches)
+                encoded = self.model.encoder(feat, feat_len) if mwer_on else None
+
                 # Note: txt should NOT start w/ <sos>
                 if not self.emb_reg:
-                    ctc_output, encode_len, att_output, att_align, dec_state = \
-                        self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt)
+                    if mwer_on:
+                        ctc_output, encode_len, att_output, att_align, dec_state = \
+                            self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt, encoded=encoded)
+                    else:
+                        ctc_output, encode_len, att_output, att_align, dec_state = \
+                            self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt)
                     total_loss, ctc_loss, att_loss, shown_loss = \
                         self.compute_losses(ctc_output, encode_len, att_output, txt, txt_len)
+                    if mwer_on:
+                        # data[3]: the transcripts on the host, as the collate function made them (no read-back)
+                        mwer_loss, mwer_stats = self.mwer(nbest, encoded[0], encode_len, data[3])
+                        mwer_loss = mwer_loss.to(torch.float32)
+                        ce_w = self.mwer.opts.ce_weight
+                        shown_loss = mwer_loss.detach() + ce_w * shown_loss
+                        total_loss = (mwer_loss if self.w_utt is None else mwer_loss * self.w_utt) + ce_w * total_loss
                 else:
                     ctc_output, encode_len, att_output, att_align, dec_state = \
                         self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt, get_dec_state=True)
@@ -193,6 +219,9 @@ class Solver(BaseSolver):
                     self.progress('Tr stat | Loss - {:.2f} | Grad. Norm - {:.2f} | {}'
                                   .format(shown_loss.detach().cpu().item(), float(grad_norm), self.timer.show()))
                     self.write_log('loss', {'tr_ctc': ctc_loss, 'tr_att': att_loss})
+                    if mwer_on:
+                        self.write_log('mwer', {'tr_exp_err': mwer_stats['exp_err'],
+                                                'tr_1best_err': mwer_stats['best_err']})
                     if self.emb_reg:
                         self.write_log('emb_loss', {'tr': emb_loss})
                         if self.emb_fuse:

@@ -1,8 +1,9 @@
-// Second-pass (n-best rescoring) kernels for gfx950: scoring only, no gradients.
+// Second-pass (n-best rescoring) kernels for gfx950: scoring only; the gradient of seq_logp lives in mwer.hip.
 //
 //   asrk_seq_logp_f32        log-probability of one target per row of [M, V] logits, and per-sequence sums, without
 //                            writing a [M, V] log_softmax: one pass over the row (running max and sum per lane),
 //                            reads the logits once and writes 4 bytes per row.
+//   asrk_seq_logp_lse_f32    the same launch with the row's log-sum-exp as one more output (what the backward needs).
 //   asrk_ctc_score_rows_f32  log p_ctc of R hypotheses against the posteriors of U < R utterances: every row walks
 //                            the frames of ITS utterance (row_mem), so the [T, V] posteriors are never repeated per
 //                            hypothesis; alpha only, no lattice is stored.
@@ -71,40 +72,58 @@ __device__ __forceinline__ float tok_value(const float *xr, int64_t tg, int V, f
 template <bool VEC>
 __global__ __launch_bounds__(256) void seq_logp_wave_kernel(const float *__restrict__ x, int64_t ldx,
                                                             const int64_t *__restrict__ target, int M, int V,
-                                                            int normalized, float *__restrict__ tok) {
+                                                            int normalized, float *__restrict__ tok,
+                                                            float *__restrict__ lse_out) {
     const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= M) return;
     const int64_t tg = target[row];
     if (tg < 0) {   // skipped row: never read
-        if (lane == 0) tok[row] = 0.f;
+        if (lane == 0) {
+            tok[row] = 0.f;
+            if (lse_out) lse_out[row] = 0.f;
+        }
         return;
     }
     const float *xr = x + (size_t)row * ldx;
     if (normalized || tg >= V) {
-        if (lane == 0) tok[row] = tok_value(xr, tg, V, 0.f);
+        if (lane == 0) {
+            tok[row] = tok_value(xr, tg, V, 0.f);
+            if (lse_out) lse_out[row] = 0.f;
+        }
         return;
     }
     const MaxSum r = ms_wave(ms_row<VEC>(xr, V, lane, 64));
-    if (lane == 0) tok[row] = tok_value(xr, tg, V, r.m + logf(r.s));
+    if (lane == 0) {
+        const float lse = r.m + logf(r.s);
+        tok[row] = tok_value(xr, tg, V, lse);
+        if (lse_out) lse_out[row] = lse;
+    }
 }
 
 // one 256-thread workgroup per row
 template <bool VEC>
 __global__ __launch_bounds__(256) void seq_logp_wg_kernel(const float *__restrict__ x, int64_t ldx,
                                                           const int64_t *__restrict__ target, int M, int V,
-                                                          int normalized, float *__restrict__ tok) {
+                                                          int normalized, float *__restrict__ tok,
+                                                          float *__restrict__ lse_out) {
     __shared__ float sm_m[4], sm_s[4];
     const int row = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t tg = target[row];   // uniform over the workgroup: every thread leaves together
     if (tg < 0) {
-        if (threadIdx.x == 0) tok[row] = 0.f;
+        if (threadIdx.x == 0) {
+            tok[row] = 0.f;
+            if (lse_out) lse_out[row] = 0.f;
+        }
         return;
     }
     const float *xr = x + (size_t)row * ldx;
     if (normalized || tg >= V) {
-        if (threadIdx.x == 0) tok[row] = tok_value(xr, tg, V, 0.f);
+        if (threadIdx.x == 0) {
+            tok[row] = tok_value(xr, tg, V, 0.f);
+            if (lse_out) lse_out[row] = 0.f;
+        }
         return;
     }
     const MaxSum w = ms_wave(ms_row<VEC>(xr, V, threadIdx.x, 256));
@@ -119,7 +138,9 @@ __global__ __launch_bounds__(256) void seq_logp_wg_kernel(const float *__restric
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (sm_m[k] > -INFINITY || sm_m[k] != sm_m[k]) s += sm_s[k] * expf(sm_m[k] - Mx);
-        tok[row] = tok_value(xr, tg, V, Mx + logf(s));
+        const float lse = Mx + logf(s);
+        tok[row] = tok_value(xr, tg, V, lse);
+        if (lse_out) lse_out[row] = lse;
     }
 }
 
@@ -311,8 +332,9 @@ static inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) 
 
 }  // namespace
 
-extern "C" int asrk_seq_logp_f32(const float *x, int64_t ldx, const int64_t *target, const int64_t *seg_off, int M,
-                                 int V, int R, int flags, float *tok_logp, double *seq_logp, void *stream) {
+// asrk_seq_logp_f32 and asrk_seq_logp_lse_f32 (lse != nullptr): the same kernels, the same arithmetic
+static int seq_logp_launch(const float *x, int64_t ldx, const int64_t *target, const int64_t *seg_off, int M, int V,
+                           int R, int flags, float *tok_logp, float *lse, double *seq_logp, void *stream) {
     if (M < 0 || V <= 0 || R < 0 || ldx < V) return ASRK_EINVAL;
     if (flags & ~ASRK_SEQ_LOGP_NORMALIZED) return ASRK_EINVAL;
     if ((seg_off == nullptr) != (seq_logp == nullptr)) return ASRK_EINVAL;
@@ -327,18 +349,18 @@ extern "C" int asrk_seq_logp_f32(const float *x, int64_t ldx, const int64_t *tar
         if (V >= SEQ_LOGP_WG_MIN_V) {
             if (vec)
                 hipLaunchKernelGGL((seq_logp_wg_kernel<true>), dim3(M), dim3(256), 0, s, x, ldx, target, M, V,
-                                   normalized, tok_logp);
+                                   normalized, tok_logp, lse);
             else
                 hipLaunchKernelGGL((seq_logp_wg_kernel<false>), dim3(M), dim3(256), 0, s, x, ldx, target, M, V,
-                                   normalized, tok_logp);
+                                   normalized, tok_logp, lse);
         } else {
             const unsigned grid = (unsigned)asrk_div_up(M, 4);
             if (vec)
                 hipLaunchKernelGGL((seq_logp_wave_kernel<true>), dim3(grid), dim3(256), 0, s, x, ldx, target, M, V,
-                                   normalized, tok_logp);
+                                   normalized, tok_logp, lse);
             else
                 hipLaunchKernelGGL((seq_logp_wave_kernel<false>), dim3(grid), dim3(256), 0, s, x, ldx, target, M, V,
-                                   normalized, tok_logp);
+                                   normalized, tok_logp, lse);
         }
     }
     if (sums)
@@ -347,6 +369,18 @@ extern "C" int asrk_seq_logp_f32(const float *x, int64_t ldx, const int64_t *tar
     asrk_prof_end_(PROF_ROWOPS, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
+}
+
+extern "C" int asrk_seq_logp_f32(const float *x, int64_t ldx, const int64_t *target, const int64_t *seg_off, int M,
+                                 int V, int R, int flags, float *tok_logp, double *seq_logp, void *stream) {
+    return seq_logp_launch(x, ldx, target, seg_off, M, V, R, flags, tok_logp, nullptr, seq_logp, stream);
+}
+
+extern "C" int asrk_seq_logp_lse_f32(const float *x, int64_t ldx, const int64_t *target, const int64_t *seg_off, int M,
+                                     int V, int R, int flags, float *tok_logp, float *lse, double *seq_logp,
+                                     void *stream) {
+    if (M > 0 && !lse) return ASRK_EINVAL;
+    return seq_logp_launch(x, ldx, target, seg_off, M, V, R, flags, tok_logp, lse, seq_logp, stream);
 }
 
 extern "C" size_t asrk_ctc_score_rows_ws_bytes(int R, int Tmax, int Lmax) {

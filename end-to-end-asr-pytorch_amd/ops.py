@@ -1495,6 +1495,81 @@ def ctc_score_rows(lp, mem_len, row_mem, targets, tgt_len, blank=0):
     return score
 
 
+# --------------------------------------------------------------------------- MWER training (csrc/mwer.hip)
+class SeqLogpFn(Function):
+    """seq_logp with a gradient: SeqLogpFn.apply(logits [M,V], target [M], seg_off [R+1], inplace=False) -> seq f64 [R]
+    (asrk_seq_logp_lse_f32: ops.seq_logp's values bit for bit).  The backward is asrk_seq_logp_bwd_f32; with
+    inplace=True it writes the gradient over the saved logits - only for a caller whose logits have no other reader
+    (the MWER scoring pass)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, seg_off, inplace=False):
+        _require_gpu(logits)
+        if logits.dim() != 2:
+            raise _lib.AsrkError("SeqLogpFn: logits must be [M, V]")
+        x = _f32c(logits)
+        M, V = x.shape
+        dev = x.device
+        tg = torch.as_tensor(target).to(device=dev, dtype=torch.int64).contiguous()
+        seg = torch.as_tensor(seg_off).to(device=dev, dtype=torch.int64).contiguous()
+        if tg.numel() != M:
+            raise _lib.AsrkError("SeqLogpFn: one target per row of the logits")
+        if seg.dim() != 1 or seg.numel() < 1:
+            raise _lib.AsrkError("SeqLogpFn: seg_off must be [R + 1]")
+        R = seg.numel() - 1
+        tok = torch.empty((M,), dtype=torch.float32, device=dev)
+        lse = torch.empty((M,), dtype=torch.float32, device=dev)
+        seq = torch.empty((R,), dtype=torch.float64, device=dev)
+        _lib.check(_L().asrk_seq_logp_lse_f32(_p(x), V, _p(tg), _p(seg), M, V, R, 0, _p(tok), _p(lse), _p(seq),
+                                              _stream()), "seq_logp_lse")
+        ctx.inplace = bool(inplace)
+        ctx.save_for_backward(x, tg, seg, lse)
+        return seq
+
+    @staticmethod
+    def backward(ctx, gseq):
+        x, tg, seg, lse = ctx.saved_tensors
+        M, V = x.shape
+        R = seg.numel() - 1
+        g = gseq.to(torch.float64).contiguous()
+        dx = x if ctx.inplace else torch.empty_like(x)
+        _lib.check(_L().asrk_seq_logp_bwd_f32(_p(x), V, _p(tg), _p(lse), _p(seg), _p(g), M, V, R, _p(dx), V,
+                                              _stream()), "seq_logp_bwd")
+        return dx, None, None, None
+
+
+class MWERLossFn(Function):
+    """MWERLossFn.apply(s f64 [N,U], err int32 [N,U], count int32 [U]) -> (loss_u f64 [U], exp_err_u f64 [U]),
+    differentiable in s through loss_u (asrk_mwer_loss_f64: the closed-form derivative comes out of the forward
+    launch); exp_err_u is a statistic and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, s, err, count):
+        _require_gpu(s)
+        if s.dim() != 2:
+            raise _lib.AsrkError("MWERLossFn: s must be [N, U]")
+        N, U = s.shape
+        dev = s.device
+        s64 = s.to(torch.float64).contiguous()
+        err = torch.as_tensor(err).to(device=dev, dtype=torch.int32).contiguous()
+        count = torch.as_tensor(count).to(device=dev, dtype=torch.int32).contiguous()
+        if err.numel() != N * U or count.numel() != U:
+            raise _lib.AsrkError("MWERLossFn: err must be [N, U] and count [U]")
+        loss = torch.empty((U,), dtype=torch.float64, device=dev)
+        ee = torch.empty((U,), dtype=torch.float64, device=dev)
+        g = torch.empty((N, U), dtype=torch.float64, device=dev)
+        _lib.check(_L().asrk_mwer_loss_f64(_p(s64), _p(err), _p(count), N, U, _p(loss), _p(ee), _p(g), _stream()),
+                   "mwer_loss")
+        ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(ee)
+        return loss, ee
+
+    @staticmethod
+    def backward(ctx, gloss, _gee):
+        g, = ctx.saved_tensors
+        return g * gloss.to(torch.float64).unsqueeze(0), None, None
+
+
 # --------------------------------------------------------------------------- cross entropy
 def _check_label_smoothing(eps):
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:

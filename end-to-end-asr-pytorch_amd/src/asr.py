@@ -87,7 +87,7 @@ class ASR(nn.Module):
         return al.states, al.tokens, al.spans, al.score, encode_len
 
     def forward(self, audio_feature, feature_len, decode_step, tf_rate=0.0, teacher=None,
-                emb_decoder=None, get_dec_state=False):
+                emb_decoder=None, get_dec_state=False, encoded=None):
         ''' Same contract as the reference (src/asr.py:72-155): returns
             (ctc_output [B,T',V] log-probs | None, encode_len [B], att_output [B,L,V] logits | None,
              att_seq [B,N,L,T'] | None, dec_state [B,L,D] | None) '''
@@ -95,7 +95,9 @@ class ASR(nn.Module):
         ctc_output, att_output, att_seq = None, None, None
         dec_state = [] if get_dec_state else None
 
-        encode_feature, encode_len = self.encoder(audio_feature, feature_len)
+        # encoded: (encode_feature, encode_len) of self.encoder(audio_feature, feature_len), when the caller ran the
+        # encoder itself because it needs the output too (MWER training scores its n-best lists on this very pass)
+        encode_feature, encode_len = self.encoder(audio_feature, feature_len) if encoded is None else encoded
 
         if self.enable_ctc:
             # (The head depends on the encoder only, like the decoder loop below, so it was tried on a second stream
@@ -343,6 +345,58 @@ class ASR(nn.Module):
         att.reset_mem()
         return tok_all[:R], seq_all[:R]
 
+    def hypothesis_logp(self, encode_feature, encode_len, ids, lens):
+        ''' score_hypotheses with a gradient (MWER training, src/mwer.py): the attention decoder's log-probability of
+            N hypotheses per utterance, teacher-forced in WHATEVER mode the module is in (training: dropout live).
+            encode_feature [U,T',D] / encode_len [U]: the encoder's output (of the training forward); ids [N*U,L] int64:
+            the hypotheses with <eos> appended, zero-padded, row n*U + u = hypothesis n of utterance u (the order of
+            RepeatBatchFn); lens [N*U]: their lengths, <eos> included.  -> s float64 [N*U], the sums of
+            log softmax(att_logits_t)[ids[r,t]] over t < lens[r], added in ascending t.
+            The key / value projections are built once per utterance and repeated by RepeatBatchFn (whose backward adds
+            the N copies in a fixed order); one loop runs over all N*U rows - the fused teacher-forced loop where
+            forward() would take it, else forward()'s step-by-step loop - then one vocabulary projection, reduced by
+            ops.SeqLogpFn, whose backward writes the gradient over the logits (nothing else reads them). '''
+        if not self.enable_att:
+            raise RuntimeError('ASR.hypothesis_logp needs the attention decoder: this model has ctc_weight = 1')
+        att, dec = self.attention, self.decoder
+        dev = encode_feature.device
+        ids = torch.as_tensor(ids).to(device=dev, dtype=torch.int64).contiguous()
+        lens = torch.as_tensor(lens).to(device=dev, dtype=torch.int64)
+        R, L = ids.shape
+        U = encode_feature.shape[0]
+        if R == 0 or L == 0 or R % U != 0:
+            raise ValueError('ASR.hypothesis_logp: ids must be [N*U, L] with N, L >= 1 (got {} rows for {} '
+                             'utterances)'.format(R, U))
+        N = R // U
+        target = torch.where(torch.arange(L, device=dev).unsqueeze(0) < lens.unsqueeze(1), ids,
+                             torch.full_like(ids, -1))
+        len_rows = encode_len.to(dev).repeat(N)
+        W = self.pre_embed.weight
+        sos_emb = dops.embedding(torch.zeros((R,), dtype=torch.long, device=dev), W)
+        teacher = self._embed_drop(dops.embedding(ids, W))
+        att.reset_mem()
+        key, value = self._speller_memory(encode_feature, encode_len)
+        key_rows, value_rows = RepeatBatchFn.apply(key, N), RepeatBatchFn.apply(value, N)
+        if sops.supported_train_loop(att, dec, self.training):
+            att.att_layer.compute_mask(key_rows, len_rows)
+            logits, _, _ = self._teacher_forced_loop(key_rows, len_rows, sos_emb, teacher, L,
+                                                     memory=(key_rows, value_rows))
+        else:
+            dec.init_state(R, max_steps=L)
+            att.load_memory(key_rows, value_rows, len_rows)
+            last_char, state_seq = sos_emb, []
+            for t in range(L):
+                _, context = att(dec.get_query(), key_rows, len_rows)
+                _, d_state = dec(dops.concat_last(last_char, context), project=False)
+                last_char = teacher[:, t, :]
+                state_seq.append(d_state)
+            states = ops.dropout(dops.stack_steps(state_seq), dec.dropout, self.training)     # [R,L,D]
+            logits = ops.linear(states, dec.char_trans.weight, dec.char_trans.bias)
+        seg = torch.arange(R + 1, dtype=torch.int64, device=dev) * L
+        s = ops.SeqLogpFn.apply(logits.reshape(R * L, self.vocab_size), target.reshape(-1), seg, True)
+        att.reset_mem()
+        return s
+
     def _greedy_loop(self, encode_feature, encode_len, sos_emb, decode_step):
         ''' argmax-feedback decoding without autograd -> (att_output [B,L,V], att_seq [B,1,L,T], states) '''
         att, dec = self.attention, self.decoder
@@ -549,12 +603,16 @@ class Attention(nn.Module):
 
     def build_memory(self, enc_feat, enc_len):
         ''' key/value cache + padded-frame mask of src/asr.py:285-304 -> (AttnTape, key, value, loc_w) '''
-        N = self.num_head
         enc_len = enc_len.to(enc_feat.device)
         self.att_layer.compute_mask(enc_feat, enc_len)
         key = ops.tanh(ops.linear(enc_feat, self.proj_k.weight, self.proj_k.bias))
         value = ops.tanh(ops.linear(enc_feat, self.proj_v.weight, self.proj_v.bias)) \
             if self.v_proj else enc_feat
+        return self._memory_tape(key, value, enc_len)
+
+    def _memory_tape(self, key, value, enc_len):
+        ''' the tape of the step-by-step loop from projected key / value rows [B,T,N*d] (the mask is already set) '''
+        N = self.num_head
         if N > 1:
             key = HeadSplitFn.apply(key, N)
             if self.v_proj:
@@ -570,6 +628,16 @@ class Attention(nn.Module):
                              self.att_layer.temperature,
                              tuple(ops._f32c(w) for w in loc_w) if loc_w else None)
         return tape, key, value, loc_w
+
+    def load_memory(self, key, value, enc_len):
+        ''' what the first forward() call of a sequence does, from key / value projections the caller already holds
+            (ASR.hypothesis_logp: projected once per utterance, then repeated per hypothesis): forward() then steps
+            over these rows and never projects the encoder output itself '''
+        enc_len = enc_len.to(key.device)
+        self.att_layer.compute_mask(key, enc_len)
+        self._tape, key, value, loc_w = self._memory_tape(key, value, enc_len)
+        self.key, self.value = key, value
+        self._token = dops.AttnHubFn.apply(self._tape, key, value, *loc_w)
 
     def forward(self, dec_state, enc_feat, enc_len):
         bs, ts, _ = enc_feat.shape

@@ -1128,7 +1128,7 @@ int asrk_ctc_align_f32(const float *lp, int64_t stride_t, int64_t stride_b, int 
                        const int64_t *target_lengths, int blank, int flags, int32_t *states, int32_t *tokens,
                        int32_t *spans, float *score, int64_t *stamps, void *ws, size_t ws_bytes, void *stream);
 
-/* ---- second-pass scoring (n-best rescoring; csrc/rescore.hip).  Inference only: no gradients. ---------------------
+/* ---- second-pass scoring (n-best rescoring; csrc/rescore.hip).  The gradient: asrk_seq_logp_bwd_f32 below. ---------
  * Token and sequence log-probabilities from logits, without a [M,V] log_softmax tensor:
  *   x [M,V] f32, row stride ldx >= V; target [M] int64;
  *   tok_logp[m] = x[m, target[m]] - logsumexp(x[m, :])  (one pass over the row: running max and sum per lane,
@@ -1144,6 +1144,36 @@ int asrk_ctc_align_f32(const float *lp, int64_t stride_t, int64_t stride_b, int 
 #define ASRK_SEQ_LOGP_NORMALIZED 1
 int asrk_seq_logp_f32(const float *x, int64_t ldx, const int64_t *target, const int64_t *seg_off, int M, int V, int R,
                       int flags, float *tok_logp, double *seq_logp, void *stream);
+
+/* asrk_seq_logp_f32 with one more output, lse[m] = logsumexp(x[m, :]) (f32 [M]; 0 for a skipped row, for
+ * target[m] >= V and with ASRK_SEQ_LOGP_NORMALIZED): the same kernels and the same arithmetic, so tok_logp and seq_logp
+ * equal asrk_seq_logp_f32's bit for bit.  lse NULL with M > 0 is ASRK_EINVAL. */
+int asrk_seq_logp_lse_f32(const float *x, int64_t ldx, const int64_t *target, const int64_t *seg_off, int M, int V,
+                          int R, int flags, float *tok_logp, float *lse, double *seq_logp, void *stream);
+
+/* ---- minimum word error rate training (csrc/mwer.hip; src/mwer.py) --------------------------------------------------
+ * Gradient of seq_logp with respect to the logits:
+ *   dx[m, v] = w_m * (1[v == target[m]] - exp(x[m, v] - lse[m])),  w_m = (float)gseq[r] for the segment r with
+ *   seg_off[r] <= m < seg_off[r+1] (seg_off [R+1] int64, non-decreasing; gseq [R] float64; lse [M] as
+ *   asrk_seq_logp_lse_f32 wrote it).  A row with target < 0, and a row in no segment, gets a row of zeros WRITTEN (dx
+ *   may be uninitialised memory) and is not read; a row with target >= V inside a segment (its forward value is NaN)
+ *   gets a row of NaN, not read either.  dx has its own row stride lddx >= V; dx == x (in place,
+ *   then lddx == ldx) is allowed: every element is read once, before it is written.  x is read once and dx written
+ *   once; the case split is asrk_seq_logp_f32's (one wave per row below 2048 columns, a workgroup per row above; 16-byte
+ *   accesses when x and dx are 16-byte aligned and both strides are multiples of 4).  No atomics.
+ * ASRK_EINVAL, before any device call: a NULL pointer with M > 0 (seg_off / gseq only when R > 0), a negative size,
+ * V <= 0, ldx < V, lddx < V, in place with lddx != ldx.  M == 0 is ASRK_OK without a launch. */
+int asrk_seq_logp_bwd_f32(const float *x, int64_t ldx, const int64_t *target, const float *lse, const int64_t *seg_off,
+                          const double *gseq, int M, int V, int R, float *dx, int64_t lddx, void *stream);
+
+/* MWER loss of U utterances over n-best lists of at most N hypotheses: s [N,U] float64 scores and err [N,U] int32 error
+ * counts, hypothesis n of utterance u at n*U + u; only n < count[u] is valid (count [U] int32, clipped to [0,N]).
+ *   p = softmax over the valid scores (max-subtracted);  exp_err_u[u] = sum p e;  loss_u[u] = sum p (e - mean e);
+ *   g[n,u] = d loss_u / d s[n,u] = p (e - exp_err_u[u]), 0 on invalid slots.  count[u] == 0: loss 0, g = 0.
+ * All outputs float64; one wave per utterance, sums by a fixed butterfly: reproducible bit for bit.
+ * ASRK_ESHAPE: N > 32; ASRK_EINVAL: a NULL pointer or a negative size; U == 0 is ASRK_OK without a launch. */
+int asrk_mwer_loss_f64(const double *s, const int32_t *err, const int32_t *count, int N, int U, double *loss_u,
+                       double *exp_err_u, double *g, void *stream);
 
 /* CTC log-likelihood of R hypotheses against the posteriors of U utterances (usually U < R): row r scores
  * targets[r, :tgt_len[r]] against the mem_len[row_mem[r]] frames of utterance row_mem[r]; frame t of utterance u at
