@@ -226,6 +226,16 @@ SIGNATURES = {
     "asrk_ctc_score_rows_ws_bytes": (c_sz, [c_int, c_int, c_int]),
     "asrk_ctc_score_rows_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
                                         c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "asrk_rnnt_joint_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
+    "asrk_rnnt_joint_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64,
+                                        c_vp]),
+    "asrk_rnnt_rows_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                   c_vp, c_vp]),
+    "asrk_rnnt_lattice_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_rnnt_grad_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8
+                           + [c_i64, c_vp]),
+    "asrk_rnnt_greedy_step_f32": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                          c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

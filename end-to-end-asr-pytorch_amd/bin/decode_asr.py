@@ -21,12 +21,18 @@ decoding (src/rescore.py): a CTC prefix beam search, then attention (+LM) rescor
 never reaches the other decoders; besides the usual two files (the beam file in rescored order) a third one,
 `..._rescore-<beam>-<ctc_weight>-<lm_weight>.csv`, lists every hypothesis with its scores.  Without the block nothing
 here changes.
+
+The optional block `decode: {transducer: {enable: true, max_symbols: 3, max_len_ratio: 0.5}}` selects batched greedy
+decoding with the RNN-transducer head (ASR.transducer_greedy; src/transducer.py) and writes the usual
+`..._output.csv`; the block never reaches the beam decoders.  The training config must have built the head (`model:
+transducer:`), otherwise the run stops with an error.  Without the block nothing here changes.
 """
 import os
 
 from . import align_asr, test_asr
 from ..parallel import gather_in_order
 from ..src.rescore import RescoreDecoder, check_decode_config
+from ..src.transducer import take_decode_block
 
 
 class _FusedGreedy:
@@ -44,6 +50,11 @@ class Solver(test_asr.Solver):
 
     def __init__(self, config, paras, mode):
         self.align = bool(config['decode'].get('align', False))
+        # taken out of the block like `rescore` below; enabled, the run takes the parent's greedy set-up (batch-wise
+        # loaders, one output file per set), whatever beam_size says: the transducer search here is greedy
+        self.transducer = take_decode_block(config['decode'])
+        if self.transducer:
+            config['decode']['beam_size'] = 1
         check_decode_config(config['decode'], config.get('emb'))
         # taken out of the block: the parent hands the whole decode block to BeamDecoder(**dcfg)
         rescore = config['decode'].pop('rescore', None) or {}
@@ -59,6 +70,20 @@ class Solver(test_asr.Solver):
             self.config['data']['corpus']['batch_size'] = 1
 
     def set_model(self):
+        if getattr(self, 'transducer', None):
+            init_adadelta = self.config['hparas']['optimizer'] == 'Adadelta'
+            self.model = test_asr.ASR(self.feat_dim, self.vocab_size, init_adadelta,
+                                      **self.config['model']).to(self.device)
+            if not self.model.enable_rnnt:
+                raise RuntimeError('decode.transducer needs a checkpoint with a transducer head: the training config '
+                                   'has no enabled `model: transducer:` block')
+            self.load_ckpt()        # eval mode
+            self.decoder = self.model
+            self.ctc_only = False
+            self.enable_att = True  # (write_hyp: transducer hypotheses are never repeat-merged)
+            self.verbose(['Decode spec| Greedy transducer decoding \t| Max symbols per frame = {} | Max len ratio = {}'
+                          .format(self.transducer['max_symbols'], self.transducer['max_len_ratio'])])
+            return
         if getattr(self, 'rescore', None):
             init_adadelta = self.config['hparas']['optimizer'] == 'Adadelta'
             self.model = test_asr.ASR(self.feat_dim, self.vocab_size, init_adadelta,
@@ -94,6 +119,24 @@ class Solver(test_asr.Solver):
             from ..src.plugin import EmbeddingRegularizer
             self.emb_decoder = EmbeddingRegularizer(self.tokenizer, self.model.dec_dim, **emb).to(self.device)
         super().load_ckpt()     # eval mode, plug-in included
+
+    def greedy_decode(self, dv_set):
+        ''' the parent's batch-wise pass; with decode.transducer the hypotheses come from ASR.transducer_greedy '''
+        if not getattr(self, 'transducer', None):
+            return super().greedy_decode(dv_set)
+        results = []
+        dv_set, batch_ids, _ = self._my_share(dv_set)
+        for k, data in enumerate(dv_set):
+            i = batch_ids[k]
+            self.progress('Valid step - {}/{}'.format(i + 1, len(dv_set)))
+            feat, feat_len, txt, txt_len = self.fetch_data(data)
+            tokens, n_tok, _ = self.model.transducer_greedy(feat, feat_len, self.transducer['max_symbols'],
+                                                            self.transducer['max_len_ratio'])
+            tokens, n_tok = tokens.tolist(), n_tok.tolist()      # one read-back per batch, after the search
+            for j in range(len(txt)):
+                idx = j + self.config['data']['corpus']['batch_size'] * i
+                results.append((str(idx), [tokens[j][:n_tok[j]]], txt[j].tolist()))
+        return results
 
     def exec(self):
         if getattr(self, 'align', False):      # (a solver assembled without __init__ decodes)

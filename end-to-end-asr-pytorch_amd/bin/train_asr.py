@@ -16,6 +16,7 @@ from ..src.data import load_dataset
 from ..src.audio import SpecAugment, SpeedPerturb, Dither, NoiseReverb
 from ..src.loss import LossOptions
 from ..src.mwer import MWEROptions, MWERLoss
+from ..src.transducer import check_exclusive
 from ..src.util import human_format, cal_er
 
 
@@ -72,6 +73,7 @@ class Solver(BaseSolver):
     def set_model(self):
         ''' Setup ASR model and optimizer '''
         init_adadelta = self.config['hparas']['optimizer'] == 'Adadelta'
+        check_exclusive(self.config)         # `model: transducer:` beside `mwer:` or `emb:` is refused
         self.model = ASR(self.feat_dim, self.vocab_size, init_adadelta, **self.config['model']).to(self.device)
         self.verbose(self.model.create_msg())
         model_paras = [{'params': self.model.parameters()}]
@@ -80,6 +82,14 @@ class Solver(BaseSolver):
         opts = LossOptions.from_config(self.config)
         self.seq_loss = ops.CrossEntropyLoss(ignore_index=0, label_smoothing=opts.label_smoothing)
         self.ctc_loss = ops.CTCLoss(blank=0, zero_infinity=opts.ctc_zero_infinity)
+        # transducer head (`model: transducer:` block; absent or disabled = the step is exactly what it was)
+        self.rnnt_on = self.model.enable_rnnt
+        if self.rnnt_on:
+            self.rnnt_loss = ops.RNNTLoss(blank=0)
+            self.best_wer['rnnt'] = 3.0
+            dec = (self.config.get('decode') or {}).get('transducer') or {}
+            self.rnnt_max_symbols = int(dec.get('max_symbols', 3))
+            self.rnnt_max_len_ratio = float(dec.get('max_len_ratio', 0.5))
         if opts.active:
             self.verbose(opts.create_msg())
         # Plug-ins (reference: bin/train_asr.py:51-63): word-embedding regulariser / embedding-fusion decoder
@@ -146,7 +156,7 @@ class Solver(BaseSolver):
     def exec(self):
         ''' Training End-to-end ASR system '''
         self.verbose('Total training steps {}.'.format(human_format(self.max_step)))
-        ctc_loss, att_loss, emb_loss = None, None, None
+        ctc_loss, att_loss, emb_loss, rnnt_loss = None, None, None, None
         n_epochs = 0
         self.timer.set()
         while self.step < self.max_step:
@@ -182,11 +192,12 @@ class Solver(BaseSolver):
                 nbest = self.mwer.nbest(feat, feat_len) if mwer_on else None
                 # the MWER step runs the encoder itself: the hypotheses are scored on the very output the training
                 # forward decodes from (ASR.forward(encoded=...): the same call it would make, so the same launches)
-                encoded = self.model.encoder(feat, feat_len) if mwer_on else None
+                # (so does the transducer step: its head reads the encoder output the CTC head reads)
+                encoded = self.model.encoder(feat, feat_len) if (mwer_on or self.rnnt_on) else None
 
                 # Note: txt should NOT start w/ <sos>
                 if not self.emb_reg:
-                    if mwer_on:
+                    if encoded is not None:
                         ctc_output, encode_len, att_output, att_align, dec_state = \
                             self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt, encoded=encoded)
                     else:
@@ -201,6 +212,15 @@ class Solver(BaseSolver):
                         ce_w = self.mwer.opts.ce_weight
                         shown_loss = mwer_loss.detach() + ce_w * shown_loss
                         total_loss = (mwer_loss if self.w_utt is None else mwer_loss * self.w_utt) + ce_w * total_loss
+                    if self.rnnt_on:
+                        # a mean over utterances like CTC: the utterance-count weight under data parallel.  The loss's
+                        # backward writes the gradient over the logits (nothing else reads them)
+                        logits = self.model.transducer_logits(encoded[0], encode_len, txt, txt_len)
+                        rnnt_loss = self.rnnt_loss(logits, txt, encode_len, txt_len, consume_logits=True)
+                        del logits
+                        shown_loss = shown_loss + rnnt_loss.detach() * self.model.rnnt_weight
+                        total_loss = total_loss + \
+                            (rnnt_loss if self.w_utt is None else rnnt_loss * self.w_utt) * self.model.rnnt_weight
                 else:
                     ctc_output, encode_len, att_output, att_align, dec_state = \
                         self.model(feat, feat_len, self.decode_step, tf_rate=tf_rate, teacher=txt, get_dec_state=True)
@@ -218,7 +238,7 @@ class Solver(BaseSolver):
                 if (self.step == 1) or (self.step % self.PROGRESS_STEP == 0):
                     self.progress('Tr stat | Loss - {:.2f} | Grad. Norm - {:.2f} | {}'
                                   .format(shown_loss.detach().cpu().item(), float(grad_norm), self.timer.show()))
-                    self.write_log('loss', {'tr_ctc': ctc_loss, 'tr_att': att_loss})
+                    self.write_log('loss', {'tr_ctc': ctc_loss, 'tr_att': att_loss, 'tr_rnnt': rnnt_loss})
                     if mwer_on:
                         self.write_log('mwer', {'tr_exp_err': mwer_stats['exp_err'],
                                                 'tr_1best_err': mwer_stats['best_err']})
@@ -255,6 +275,8 @@ class Solver(BaseSolver):
         if self.emb_decoder is not None:
             self.emb_decoder.eval()
         dev_wer = {'att': [], 'ctc': []}
+        if self.rnnt_on:
+            dev_wer['rnnt'] = []
         for i, data in enumerate(self.dv_set):
             self.progress('Valid step - {}/{}'.format(i + 1, len(self.dv_set)))
             feat, feat_len, txt, txt_len = self.fetch_data(data)
@@ -268,6 +290,11 @@ class Solver(BaseSolver):
                                    emb_decoder=self.emb_decoder)
             dev_wer['att'].append(cal_er(self.tokenizer, att_output, txt))
             dev_wer['ctc'].append(cal_er(self.tokenizer, ctc_output, txt, ctc=True))
+            if self.rnnt_on:
+                with torch.no_grad():
+                    rnnt_tok, _, _ = self.model.transducer_greedy(feat, feat_len, self.rnnt_max_symbols,
+                                                                  self.rnnt_max_len_ratio)
+                dev_wer['rnnt'].append(cal_er(self.tokenizer, rnnt_tok, txt))
 
             # Log some examples
             if i == len(self.dv_set) // 2:
@@ -282,7 +309,7 @@ class Solver(BaseSolver):
                             ops.argmax(ctc_output[j]).tolist(), ignore_repeat=True))
 
         # Ckpt if performance improves
-        for task in ['att', 'ctc']:
+        for task in list(dev_wer):
             dev_wer[task] = sum(dev_wer[task]) / len(dev_wer[task])
             if dev_wer[task] < self.best_wer[task]:
                 self.best_wer[task] = dev_wer[task]

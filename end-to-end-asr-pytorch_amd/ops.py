@@ -1570,6 +1570,153 @@ class MWERLossFn(Function):
         return g * gloss.to(torch.float64).unsqueeze(0), None, None
 
 
+# --------------------------------------------------------------------------- RNN-transducer (csrc/rnnt.hip)
+class RNNTLossFn(Function):
+    """RNNTLossFn.apply(logits [B,T,U+1,V], targets [B,L], enc_len [B], txt_len [B], blank, reduction,
+    consume_logits=False): the transducer loss (Graves 2012) on unnormalised joint logits.  The forward reads the logits
+    once (asrk_rnnt_rows_f32) and runs the lattice; it saves lse, the blank / label log-probabilities, alpha, beta and
+    nll, never a [.., V] log_softmax.  The backward reads them once more and writes the closed-form gradient
+    (asrk_rnnt_grad_f32); with consume_logits=True it writes over the logits' own storage and returns that tensor: the
+    logits are dead afterwards, so only a caller whose logits have no other reader may ask for it."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, enc_len, txt_len, blank=0, reduction="mean", consume_logits=False):
+        _require_gpu(logits)
+        if logits.dim() != 4:
+            raise _lib.AsrkError("RNNTLoss: logits must be [B, T, U + 1, V]")
+        x = _f32c(logits)
+        B, T, U1, V = x.shape
+        dev = x.device
+        txt = torch.as_tensor(targets).to(device=dev, dtype=torch.int64)
+        if txt.dim() != 2 or txt.shape[0] != B or txt.shape[1] < U1 - 1:
+            raise _lib.AsrkError("RNNTLoss: targets must be [B, L] with L >= U")
+        txt = txt.contiguous()
+        el = torch.as_tensor(enc_len).to(device=dev, dtype=torch.int64).contiguous()
+        tl = torch.as_tensor(txt_len).to(device=dev, dtype=torch.int64).contiguous()
+        if el.numel() != B or tl.numel() != B:
+            raise _lib.AsrkError("RNNTLoss: one enc_len and one txt_len per utterance")
+        L = _L()
+        lse = torch.empty((B, T, U1), dtype=torch.float32, device=dev)
+        lpb, lpl, alpha = torch.empty_like(lse), torch.empty_like(lse), torch.empty_like(lse)
+        beta = torch.empty_like(lse) if ctx.needs_input_grad[0] else None   # alpha alone when no gradient is wanted
+        nll = torch.empty((B,), dtype=torch.float32, device=dev)
+        _lib.check(L.asrk_rnnt_rows_f32(_p(x), V, _p(txt), txt.shape[1], _p(el), _p(tl), B, T, U1, V, blank, _p(lse),
+                                        _p(lpb), _p(lpl), _stream()), "rnnt_rows")
+        _lib.check(L.asrk_rnnt_lattice_f32(_p(lpb), _p(lpl), _p(el), _p(tl), B, T, U1, _p(alpha), _p(beta), _p(nll),
+                                           _stream()), "rnnt_lattice")
+        ctx.save_for_backward(x, txt, el, tl, lse, lpb, lpl, alpha, beta, nll)
+        ctx.meta = (blank, reduction, bool(consume_logits))
+        if reduction == "mean":
+            return nll.mean()
+        if reduction == "sum":
+            return nll.sum()
+        return nll
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, txt, el, tl, lse, lpb, lpl, alpha, beta, nll = ctx.saved_tensors
+        blank, reduction, consume = ctx.meta
+        B, T, U1, V = x.shape
+        g = gout.to(torch.float32)
+        if reduction == "mean":
+            gscale = (g / B).expand(B)
+        elif reduction == "sum":
+            gscale = g.expand(B)
+        else:
+            gscale = g
+        gscale = gscale.contiguous()
+        dz = x if consume else torch.empty_like(x)
+        _lib.check(_L().asrk_rnnt_grad_f32(_p(x), V, _p(txt), txt.shape[1], _p(el), _p(tl), B, T, U1, V, blank, _p(lse),
+                                           _p(lpb), _p(lpl), _p(alpha), _p(beta), _p(nll), _p(gscale), _p(dz), V,
+                                           _stream()), "rnnt_grad")
+        return dz, None, None, None, None, None, None
+
+
+class RNNTLoss(torch.nn.Module):
+    """Transducer loss on joint logits [B, T, U+1, V] (not log-probabilities: the normalisation happens inside).
+    'mean' is the mean over the B utterances of nll_b, not length-normalised.  forward(..., consume_logits=True) lets
+    the backward overwrite the logits with their gradient: the logits are dead after backward()."""
+
+    def __init__(self, blank=0, reduction="mean"):
+        super().__init__()
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError("RNNTLoss: unknown reduction %r" % (reduction,))
+        self.blank = blank
+        self.reduction = reduction
+
+    def forward(self, logits, targets, enc_len, txt_len, consume_logits=False):
+        return RNNTLossFn.apply(logits, targets, enc_len, txt_len, self.blank, self.reduction, consume_logits)
+
+
+class RNNTJointFn(Function):
+    """RNNTJointFn.apply(E [B,T,J], P [B,U+1,J]) -> H [B,T,U+1,J] = tanh(E[b,t] + P[b,u]) (asrk_rnnt_joint_f32); the
+    backward sums dH * (1 - H^2) over u into dE and over t into dP (asrk_rnnt_joint_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, E, P):
+        _require_gpu(E)
+        E, P = _f32c(E), _f32c(P)
+        if E.dim() != 3 or P.dim() != 3 or E.shape[0] != P.shape[0] or E.shape[2] != P.shape[2]:
+            raise _lib.AsrkError("RNNTJointFn: E must be [B, T, J] and P [B, U + 1, J]")
+        B, T, J = E.shape
+        U1 = P.shape[1]
+        H = torch.empty((B, T, U1, J), dtype=torch.float32, device=E.device)
+        _lib.check(_L().asrk_rnnt_joint_f32(_p(E), J, _p(P), J, None, B, T, U1, J, _p(H), J, _stream()), "rnnt_joint")
+        ctx.save_for_backward(H)
+        return H
+
+    @staticmethod
+    def backward(ctx, dH):
+        H, = ctx.saved_tensors
+        B, T, U1, J = H.shape
+        dH = _f32c(dH)
+        dE = torch.empty((B, T, J), dtype=torch.float32, device=H.device)
+        dP = torch.empty((B, U1, J), dtype=torch.float32, device=H.device)
+        _lib.check(_L().asrk_rnnt_joint_bwd_f32(_p(H), J, _p(dH), J, B, T, U1, J, _p(dE), J, _p(dP), J, _stream()),
+                   "rnnt_joint_bwd")
+        return dE, dP
+
+
+@torch.no_grad()
+def rnnt_joint_step(E, P, t_idx):
+    """the decode form of the joint: tanh(E[b, t_idx[b]] + P[b]) -> [B, J]; E [B,T,J], P [B,J], t_idx int32 [B]
+    (clamped to the last frame by the kernel)"""
+    _require_gpu(E)
+    E, P = _f32c(E), _f32c(P)
+    B, T, J = E.shape
+    if P.shape != (B, J) or t_idx.dtype != torch.int32 or t_idx.numel() != B:
+        raise _lib.AsrkError("rnnt_joint_step: P must be [B, J] and t_idx int32 [B]")
+    H = torch.empty((B, J), dtype=torch.float32, device=E.device)
+    _lib.check(_L().asrk_rnnt_joint_f32(_p(E), J, _p(P), J, _p(t_idx), B, T, 1, J, _p(H), J, _stream()),
+               "rnnt_joint_step")
+    return H
+
+
+RNNTGreedyState = collections.namedtuple("RNNTGreedyState",
+                                         ["t_ptr", "n_sym", "n_tok", "tokens", "last_tok", "emit", "done"])
+
+
+def rnnt_greedy_state(B, max_len, device):
+    """the device-resident bookkeeping of the greedy search, at its start: frame 0, nothing emitted, <sos> = 0 last"""
+    i32 = lambda: torch.zeros((B,), dtype=torch.int32, device=device)   # noqa: E731
+    return RNNTGreedyState(i32(), i32(), i32(), torch.zeros((B, max(max_len, 1)), dtype=torch.int64, device=device),
+                           torch.zeros((B,), dtype=torch.int64, device=device), i32(), i32())
+
+
+@torch.no_grad()
+def rnnt_greedy_step(logits, enc_len, T, state, max_symbols, max_len, blank=0):
+    """one lock-step iteration (asrk_rnnt_greedy_step_f32) on logits [B, V]: updates `state` in place, reads nothing
+    back.  enc_len int64 [B] on the device; T the padded frame count."""
+    _require_gpu(logits)
+    x = _f32c(logits)
+    B, V = x.shape
+    s = state
+    _lib.check(_L().asrk_rnnt_greedy_step_f32(_p(x), V, _p(enc_len), B, T, V, blank, max_symbols, max_len, _p(s.t_ptr),
+                                              _p(s.n_sym), _p(s.n_tok), _p(s.tokens), s.tokens.shape[1],
+                                              _p(s.last_tok), _p(s.emit), _p(s.done), _stream()), "rnnt_greedy_step")
+    return state
+
+
 # --------------------------------------------------------------------------- cross entropy
 def _check_label_smoothing(eps):
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:

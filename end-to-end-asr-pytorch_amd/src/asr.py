@@ -10,6 +10,7 @@ from .. import ops
 from .. import decoder_ops as dops
 from .. import speller_ops as sops
 from .util import init_weights, init_gate
+from .transducer import TransducerHead, transducer_enabled
 from .module import (VGGExtractor, CNNExtractor, RNNLayer, RNNParams, ScaleDotAttention,
                      LocationAwareAttention)
 
@@ -21,7 +22,7 @@ class ASR(nn.Module):
     ''' ASR model, including Encoder/Decoder(s) (reference: src/asr.py:12-155) '''
 
     def __init__(self, input_size, vocab_size, init_adadelta, ctc_weight, encoder, attention,
-                 decoder, emb_drop=0.0):
+                 decoder, emb_drop=0.0, transducer=None):
         super(ASR, self).__init__()
 
         assert 0 <= ctc_weight <= 1
@@ -41,6 +42,16 @@ class ASR(nn.Module):
             self.decoder = Decoder(self.encoder.out_dim + self.dec_dim, vocab_size, **decoder)
             query_dim = self.dec_dim * self.decoder.layer
             self.attention = Attention(self.encoder.out_dim, query_dim, **attention)
+        # RNN-transducer head (the `model: transducer:` block; absent or enable: false = no new parameter, no new key)
+        self.enable_rnnt = transducer_enabled(transducer)
+        self.rnnt_weight = 0.0
+        if self.enable_rnnt:
+            unknown = sorted(set(transducer) - {'enable', 'weight', 'joint_dim', 'pred'}, key=str)
+            if unknown:
+                raise ValueError('model.transducer: unknown key(s) {}'.format(unknown))
+            self.rnnt_weight = float(transducer.get('weight', 0.3))
+            self.transducer = TransducerHead(vocab_size, self.encoder.out_dim, dict(transducer.get('pred') or {}),
+                                             int(transducer.get('joint_dim', 512)))
 
         if init_adadelta:
             self.apply(init_weights)
@@ -68,7 +79,31 @@ class ASR(nn.Module):
         if self.enable_att:
             msg.append('           | {} attention decoder enabled ( lambda = {}).'.format(
                 self.attention.mode, 1 - self.ctc_weight))
+        if self.enable_rnnt:
+            msg.append(self.transducer.create_msg())
         return msg
+
+    def _need_transducer(self, what):
+        if not self.enable_rnnt:
+            raise RuntimeError('ASR.{} needs a transducer head: this model was built without the '
+                               '`model: transducer:` block'.format(what))
+
+    def transducer_logits(self, encode_feature, encode_len, txt, txt_len):
+        ''' joint logits [B,T',U+1,V] of the transducer head on the encoder's output (of the training forward:
+            ASR.forward(encoded=...)), for ops.RNNTLoss(consume_logits=True); txt [B,L] padded labels, txt_len [B] '''
+        self._need_transducer('transducer_logits')
+        return self.transducer(encode_feature, encode_len, txt, txt_len)
+
+    @torch.no_grad()
+    def transducer_greedy(self, audio_feature, feature_len, max_symbols=3, max_len_ratio=0.5):
+        ''' batched greedy transducer decoding: encoder -> TransducerHead.greedy with at most max_symbols tokens per
+            encoder frame and ceil(max_len_ratio * T') tokens per utterance.
+            Returns (tokens int64 [B, max_len] zero-padded, n_tokens int32 [B], encode_len [B]), all on the device '''
+        self._need_transducer('transducer_greedy')
+        encode_feature, encode_len = self.encoder(audio_feature, feature_len)
+        max_len = max(1, int(np.ceil(encode_feature.shape[1] * float(max_len_ratio))))
+        tokens, n_tok = self.transducer.greedy(encode_feature, encode_len, max_symbols, max_len)
+        return tokens, n_tok, encode_len
 
     @torch.no_grad()
     def ctc_align(self, audio_feature, feature_len, txt, txt_len, packed=False):

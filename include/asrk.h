@@ -1195,6 +1195,67 @@ int asrk_ctc_score_rows_f32(const float *lp, int64_t stride_u, int64_t stride_t,
                             int Lmax, const int64_t *tgt_len, int R, int blank, float *score, void *ws, size_t ws_bytes,
                             void *stream);
 
+/* ---- RNN-transducer head (csrc/rnnt.hip, csrc/rnnt.inc; src/transducer.py) --------------------------------------------
+ * Shapes: B utterances, T encoder frames, U1 = U + 1 prediction rows (U = padded label count), V outputs, J joint
+ * width.  Cell (b, t, u) is row (b*T + t)*U1 + u of every [B,T,U1,...] array.  enc_len, txt_len [B] and txt
+ * [B, txt_stride] (txt_stride >= U; the labels y_1..y_U of utterance b are txt[b, 0..U_b-1]) are int64 device arrays;
+ * the kernels clamp the lengths to 1 <= T_b <= T and 0 <= U_b <= U, so a bad length never indexes outside a buffer.
+ * All values f32.  No float atomics: every result is a pure function of its inputs, reproducible bit for bit.
+ * 16-byte accesses when every base is 16-byte aligned and every row stride (and J) is a multiple of 4, scalar otherwise.
+ * ASRK_EINVAL, before any device call: a NULL pointer with B > 0, a negative size, T, U1, V or J <= 0, a row stride
+ * below the row length, blank outside [0,V), txt_stride < U.  ASRK_ESHAPE: B*T*U1 > INT32_MAX.  B == 0: ASRK_OK.
+ *
+ * Joint network: H[b,t,u,:] = tanh(E[b,t,:] + P[b,u,:]); E [B,T,J] row stride lde, P [B,U1,J] row stride ldp,
+ * H [B,T,U1,J] row stride ldh.  With t_idx (int32 [B], clamped to [0,T-1]) the decode form: H [B,U1,J] from frame
+ * t_idx[b] of utterance b alone (U1 = 1 in the greedy search).  Call site: ops.RNNTJointFn, ops.rnnt_joint_step. */
+int asrk_rnnt_joint_f32(const float *E, int64_t lde, const float *P, int64_t ldp, const int32_t *t_idx, int B, int T,
+                        int U1, int J, float *H, int64_t ldh, void *stream);
+/* dE[b,t,:] = sum_u dH[b,t,u,:] * (1 - H^2), dP[b,u,:] = sum_t dH[b,t,u,:] * (1 - H^2): one thread owns an output
+ * element and adds its terms in ascending u (t).  Padded cells need no mask: their dH is zero as asrk_rnnt_grad_f32
+ * writes it.  H and dH are read twice (once per output).  Call site: ops.RNNTJointFn.backward. */
+int asrk_rnnt_joint_bwd_f32(const float *H, int64_t ldh, const float *dH, int64_t lddh, int B, int T, int U1, int J,
+                            float *dE, int64_t ldde, float *dP, int64_t lddp, void *stream);
+/* Row pass, the first of two reads of the logits z [B*T*U1, V] (row stride ldz): per cell inside the lattice
+ *   lse = logsumexp(z[row, :]) (one pass: running max and sum per lane, as asrk_seq_logp_f32),
+ *   lpb = z[row, blank] - lse,  lpl = z[row, txt[b, u]] - lse for u < U_b (0 at u = U_b; NaN for a label outside [0,V),
+ *   nothing read).  A cell outside the lattice (t >= T_b or u > U_b) gets three zeros and its row is never read.
+ * One wave per row below V = 2048 (4 rows per workgroup), a 256-thread workgroup per row from there on.
+ * Call site: ops.RNNTLossFn.forward. */
+int asrk_rnnt_rows_f32(const float *z, int64_t ldz, const int64_t *txt, int64_t txt_stride, const int64_t *enc_len,
+                       const int64_t *txt_len, int B, int T, int U1, int V, int blank, float *lse, float *lpb,
+                       float *lpl, void *stream);
+/* Lattice: alpha(0,0) = 0, alpha(t,u) = logaddexp(alpha(t-1,u) + lpb(t-1,u), alpha(t,u-1) + lpl(t,u-1));
+ * beta(T_b-1,U_b) = lpb, beta(t,u) = logaddexp(lpb(t,u) + beta(t+1,u), lpl(t,u) + beta(t,u+1));
+ * nll[b] = -(alpha(T_b-1,U_b) + lpb(T_b-1,U_b)).  One workgroup per utterance walks the T_b + U_b anti-diagonals, 128
+ * lanes per direction (a lane loop when U1 > 128), alpha and beta concurrently in the same launch, the previous
+ * diagonal in LDS.  alpha, beta [B,T,U1]: cells outside the lattice are not written.  beta == NULL: alpha alone (no
+ * gradient wanted).  ASRK_ESHAPE: U1 > 2048.  Call site: ops.RNNTLossFn.forward. */
+int asrk_rnnt_lattice_f32(const float *lpb, const float *lpl, const int64_t *enc_len, const int64_t *txt_len, int B,
+                          int T, int U1, float *alpha, float *beta, float *nll, void *stream);
+/* Gradient pass, the second and last read of the logits:
+ *   dz[b,t,u,v] = gscale[b] * (exp(alpha + beta - lnP) * softmax_v - [v == blank] exp(alpha + lpb + beta(t+1,u) - lnP)
+ *                              - [v == y_{u+1}] exp(alpha + lpl + beta(t,u+1) - lnP)),
+ * beta(T_b,U_b) := 0 and every other beta outside the lattice -inf.  Cells outside the lattice get exact zeros WRITTEN
+ * (dz may be uninitialised) and are not read.  dz has its own row stride lddz >= V; dz == z (in place, then
+ * lddz == ldz) is allowed: every element is read once, before it is written, and lpb / lpl come from the row pass.
+ * The case split is asrk_rnnt_rows_f32's.  Call site: ops.RNNTLossFn.backward. */
+int asrk_rnnt_grad_f32(const float *z, int64_t ldz, const int64_t *txt, int64_t txt_stride, const int64_t *enc_len,
+                       const int64_t *txt_len, int B, int T, int U1, int V, int blank, const float *lse,
+                       const float *lpb, const float *lpl, const float *alpha, const float *beta, const float *nll,
+                       const float *gscale, float *dz, int64_t lddz, void *stream);
+/* One iteration of the lock-step greedy search: k = argmax of logits[b, :V] (row stride ld; the lowest index among
+ * equal values), then per row with done[b] == 0:
+ *   k == blank, or n_sym[b] >= max_symbols, or n_tok[b] >= max_len: t_ptr[b] += 1, n_sym[b] = 0, emit[b] = 0, and
+ *   done[b] = 1 once t_ptr[b] >= T_b (nothing is emitted);
+ *   otherwise tokens[b, n_tok[b]] = k, n_tok[b] += 1, n_sym[b] += 1, last_tok[b] = k, emit[b] = 1.
+ * A row with done[b] != 0 is not read; only emit[b] = 0 is written.  t_ptr, n_sym, n_tok, emit, done: int32 [B];
+ * tokens int64 [B, tok_stride] (tok_stride >= max_len), last_tok int64 [B]; all device-resident, nothing is read back.
+ * One wave per row.  Call site: ops.rnnt_greedy_step. */
+int asrk_rnnt_greedy_step_f32(const float *logits, int64_t ld, const int64_t *enc_len, int B, int T, int V, int blank,
+                              int max_symbols, int max_len, int32_t *t_ptr, int32_t *n_sym, int32_t *n_tok,
+                              int64_t *tokens, int64_t tok_stride, int64_t *last_tok, int32_t *emit, int32_t *done,
+                              void *stream);
+
 /* ---- CTC prefix scores for joint CTC-attention beam search (src/ctc.py:76-116) -----------
  * All (hypothesis h, candidate c) pairs of one beam step in one launch.  x [T,V] log-probs;
  * r_prev [n,T,2] (0 = non-blank, 1 = blank path) of each hypothesis' prefix g_h; prefix_len[h] =
