@@ -216,6 +216,7 @@ SIGNATURES = {
     "asrk_ctc_loss_bwd_ex_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int,
                                          c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                          c_i64, c_int, c_vp]),
+    "asrk_ctc_loss_plan_info": (c_int, [c_int, c_int, c_int, c_vp, c_int]),
     "asrk_ctc_align_ws_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "asrk_ctc_align_f32": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_int,
                                    c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

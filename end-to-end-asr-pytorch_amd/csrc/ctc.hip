@@ -17,6 +17,38 @@ namespace {
 
 constexpr int CTC_THREADS = 64;
 constexpr int CTC_MAX_SPL = 32;  // states per lane -> S <= 2048 (L <= 1023)
+constexpr int GATHER_ROWS = 8;   // frames per ctc_gather_kernel workgroup
+
+// What the loss launches do for a shape: the one place the dispatch arithmetic lives (both launchers and
+// asrk_ctc_loss_plan_info read it).
+struct CtcPlan {
+    int spl_tmpl;     // ctc_lattice_kernel's states-per-lane template: 4, 16 or CTC_MAX_SPL
+    int fast;         // its FAST flag (hardware exp / log): short lattices only
+    int spl;          // states per lane in use, ceil(Smax / 64) <= spl_tmpl
+    int gather_y;     // ctc_gather_kernel grid y (0: no launch)
+    int t_per_block;  // ctc_grad_fix_kernel: frames per workgroup (a multiple of 4) and
+    int tchunks;      //   its grid y; both 0 where the backward launches nothing
+    int dense_grid;   // ctc_grad_dense_kernel grid x (4 rows of [T*B] per workgroup)
+};
+
+inline CtcPlan ctc_plan(int T, int B, int Lmax) {
+    CtcPlan pl{};
+    const int Smax = 2 * Lmax + 1;
+    pl.spl_tmpl = Smax <= CTC_THREADS * 4 ? 4 : Smax <= CTC_THREADS * 16 ? 16 : CTC_MAX_SPL;
+    // T > 512 or more than 256 states: library expf / logf (see lse3)
+    pl.fast = (Smax <= CTC_THREADS * 4 && T <= 512) ? 1 : 0;
+    pl.spl = asrk_div_up(Smax, CTC_THREADS);
+    if (B <= 0) return pl;
+    pl.gather_y = asrk_div_up(T, GATHER_ROWS);
+    if (T <= 0) return pl;
+    int tchunks = asrk_div_up(512, B);
+    if (tchunks > asrk_div_up(T, 4)) tchunks = asrk_div_up(T, 4);
+    if (tchunks < 1) tchunks = 1;
+    pl.t_per_block = asrk_div_up(asrk_div_up(T, tchunks), 4) * 4;
+    pl.tchunks = asrk_div_up(T, pl.t_per_block);
+    pl.dense_grid = asrk_div_up(T * B, 4);
+    return pl;
+}
 
 template <bool FAST>
 __device__ __forceinline__ float lse3(float a, float b, float c) {
@@ -69,7 +101,6 @@ __device__ __forceinline__ int ext_label(const int64_t *tgt, int s, int blank) {
 
 // K0: lpg[b][t][s] = lp[t, b, ext_b[s]] for t < T_b, s < S_b.  Fully parallel scattered gather; every
 // later CTC kernel reads these compact rows (coalesced, L2-resident) instead of the [T,B,V] tensor.
-constexpr int GATHER_ROWS = 8;
 __global__ __launch_bounds__(256) void ctc_gather_kernel(CtcArgs p) {
     const int b = blockIdx.x;
     const int Smax = 2 * p.Lmax + 1;
@@ -218,7 +249,9 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(CtcArgs p) {
     }
 }
 
-// dense part: grad = exp(lp) * scale (t < T_b) or 0; with zero_inf every row of an utterance whose nll is +inf is 0
+// dense part: grad = exp(lp) * scale (t < T_b) or 0; with zero_inf every row of an utterance whose nll is +inf is 0.
+// An utterance the lattice flagged (nll NaN: a label outside [0,V), its alpha / beta rows were never written) gets NaN
+// in every element of its frames t < T_b, so the gradient norm is NaN and the solver skips the step.
 __global__ __launch_bounds__(256) void ctc_grad_dense_kernel(const float *__restrict__ lp,
                                                              int64_t st, int64_t sb, int T, int B,
                                                              int V, const int64_t *in_len,
@@ -231,7 +264,9 @@ __global__ __launch_bounds__(256) void ctc_grad_dense_kernel(const float *__rest
     const int t = row / B, b = row - t * B;
     const float *x = lp + (int64_t)t * st + (int64_t)b * sb;
     float *g = grad + (int64_t)t * gst + (int64_t)b * gsb;
-    const bool live = t < (int)in_len[b] && !(zero_inf && nll[b] == INFINITY);
+    const float nl = nll[b];
+    const bool live = t < (int)in_len[b] && !(zero_inf && nl == INFINITY);
+    const bool flagged = nl != nl;
     const float sc = gscale[b];
     const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15) == 0 &&
                      (V % 4 == 0);
@@ -239,7 +274,9 @@ __global__ __launch_bounds__(256) void ctc_grad_dense_kernel(const float *__rest
         const int nv = V >> 2;
         for (int i = lane; i < nv; i += 64) {
             f32x4 o = {0.f, 0.f, 0.f, 0.f};
-            if (live) {
+            if (live && flagged) {
+                o[0] = nl; o[1] = nl; o[2] = nl; o[3] = nl;
+            } else if (live) {
                 const f32x4 v = reinterpret_cast<const f32x4 *>(x)[i];
                 o[0] = expf(v[0]) * sc; o[1] = expf(v[1]) * sc;
                 o[2] = expf(v[2]) * sc; o[3] = expf(v[3]) * sc;
@@ -247,7 +284,7 @@ __global__ __launch_bounds__(256) void ctc_grad_dense_kernel(const float *__rest
             reinterpret_cast<f32x4 *>(g)[i] = o;
         }
     } else {
-        for (int i = lane; i < V; i += 64) g[i] = live ? expf(x[i]) * sc : 0.f;
+        for (int i = lane; i < V; i += 64) g[i] = !live ? 0.f : flagged ? nl : expf(x[i]) * sc;
     }
 }
 
@@ -273,6 +310,9 @@ __global__ __launch_bounds__(256) void ctc_grad_fix_kernel(CtcFixArgs p) {
     // zeroed utterance: the dense pass wrote 0 to all of its rows and the label columns stay 0 (nothing is
     // computed from the +inf, so no inf * 0); the whole workgroup shares b and leaves together
     if (p.zero_inf && p.nll[b] == INFINITY) return;
+    // flagged utterance (NaN nll): its frames are NaN from the dense pass.  The labels that caused the flag lie outside
+    // [0,V) and must never become a column index, and its alpha / beta rows were never written.
+    if (p.nll[b] != p.nll[b]) return;
     const int Smax = 2 * p.Lmax + 1;
     int *ext = sm_i;                 // [Smax]
     int *nxt = sm_i + Smax;          // [Smax] next state with the same label (or -1)
@@ -344,6 +384,23 @@ __global__ __launch_bounds__(256) void ctc_grad_fix_kernel(CtcFixArgs p) {
 
 }  // namespace
 
+extern "C" int asrk_ctc_loss_plan_info(int T, int B, int Lmax, int *info, int n) {
+    if (!info || n < ASRK_CTC_LOSS_PLAN_INFO_LEN) return ASRK_EINVAL;
+    for (int i = 0; i < n; ++i) info[i] = 0;
+    if (T < 0 || B < 0 || Lmax < 0) return ASRK_EINVAL;
+    if (Lmax > (CTC_THREADS * CTC_MAX_SPL - 1) / 2) return ASRK_ESHAPE;
+    const CtcPlan pl = ctc_plan(T, B, Lmax);
+    info[0] = pl.spl_tmpl;
+    info[1] = pl.fast;
+    info[2] = pl.spl;
+    info[3] = pl.gather_y;
+    info[4] = pl.t_per_block;
+    info[5] = pl.tchunks;
+    info[6] = pl.dense_grid;
+    info[7] = 2 * Lmax + 1;
+    return ASRK_OK;
+}
+
 extern "C" int asrk_ctc_loss_fwd_f32(const float *lp, int64_t stride_t, int64_t stride_b, int T,
                                      int B, int V, const int64_t *targets, int64_t tgt_stride,
                                      int Lmax, const int64_t *input_lengths,
@@ -372,14 +429,15 @@ extern "C" int asrk_ctc_loss_fwd_ex_f32(const float *lp, int64_t stride_t, int64
               target_lengths, blank, alpha, beta, lpg, nll, loss, loss ? n_infeasible : nullptr,
               (flags & ASRK_CTC_ZERO_INFINITY) ? 1 : 0};
     asrk_prof_begin_(PROF_CTC, s);
-    if (T > 0)
-        hipLaunchKernelGGL(ctc_gather_kernel, dim3(B, asrk_div_up(T, GATHER_ROWS)), dim3(256), 0, s, a);
+    const CtcPlan pl = ctc_plan(T, B, Lmax);
+    if (pl.gather_y > 0)
+        hipLaunchKernelGGL(ctc_gather_kernel, dim3(B, pl.gather_y), dim3(256), 0, s, a);
     const dim3 grid(B, beta ? 2 : 1);
-    if (Smax <= CTC_THREADS * 4 && T <= 512)
+    if (pl.spl_tmpl == 4 && pl.fast)
         hipLaunchKernelGGL((ctc_lattice_kernel<4, true>), grid, dim3(CTC_THREADS), 2 * Smax * sizeof(float), s, a);
-    else if (Smax <= CTC_THREADS * 4)
+    else if (pl.spl_tmpl == 4)
         hipLaunchKernelGGL((ctc_lattice_kernel<4, false>), grid, dim3(CTC_THREADS), 2 * Smax * sizeof(float), s, a);
-    else if (Smax <= CTC_THREADS * 16)
+    else if (pl.spl_tmpl == 16)
         hipLaunchKernelGGL((ctc_lattice_kernel<16, false>), grid, dim3(CTC_THREADS), 2 * Smax * sizeof(float), s, a);
     else   // character-level transcripts of the longest LibriSpeech utterances (L up to 1023)
         hipLaunchKernelGGL((ctc_lattice_kernel<CTC_MAX_SPL, false>), grid, dim3(CTC_THREADS),
@@ -420,17 +478,13 @@ extern "C" int asrk_ctc_loss_bwd_ex_f32(const float *lp, int64_t stride_t, int64
     // dense gradient: every log-prob read, every gradient element written (the lattice itself is a few MB)
     asrk_prof_work_(PROF_CTC, 8.0 * (double)T * (double)B * (double)V);
     asrk_prof_begin_(PROF_CTC, s);
-    hipLaunchKernelGGL(ctc_grad_dense_kernel, dim3(asrk_div_up(T * B, 4)), dim3(256), 0, s, lp,
+    const CtcPlan pl = ctc_plan(T, B, Lmax);
+    hipLaunchKernelGGL(ctc_grad_dense_kernel, dim3(pl.dense_grid), dim3(256), 0, s, lp,
                        stride_t, stride_b, T, B, V, input_lengths, gscale, grad, g_stride_t,
                        g_stride_b, nll, zero_inf);
-    int tchunks = asrk_div_up(512, B);
-    if (tchunks > asrk_div_up(T, 4)) tchunks = asrk_div_up(T, 4);
-    if (tchunks < 1) tchunks = 1;
-    const int tpb = asrk_div_up(asrk_div_up(T, tchunks), 4) * 4;
-    tchunks = asrk_div_up(T, tpb);
     CtcFixArgs f{T, B, targets, tgt_stride, Lmax, input_lengths, target_lengths, blank, alpha, beta,
-                 lpg, nll, gscale, grad, g_stride_t, g_stride_b, tpb, zero_inf};
-    hipLaunchKernelGGL(ctc_grad_fix_kernel, dim3(B, tchunks), dim3(256),
+                 lpg, nll, gscale, grad, g_stride_t, g_stride_b, pl.t_per_block, zero_inf};
+    hipLaunchKernelGGL(ctc_grad_fix_kernel, dim3(B, pl.tchunks), dim3(256),
                        (size_t)Smax * (3 * sizeof(int) + 4 * sizeof(float)), s, f);
     asrk_prof_end_(PROF_CTC, s);
     ASRK_LAUNCH_CHECK();

@@ -1268,7 +1268,13 @@ CTC_ZERO_INFINITY = 1      # ASRK_CTC_ZERO_INFINITY (include/asrk.h)
 class CTCLossFn(Function):
     """torch.nn.CTCLoss(blank, reduction='mean') (reference: bin/train_asr.py:49,123-124).  zero_infinity=True: an
     utterance with no path through its frames (nll = +inf) contributes loss 0 and an all-zero gradient; 'mean' still
-    divides by all B utterances.  `count_out`: optional int32 device scalar that receives the number zeroed."""
+    divides by all B utterances.  `count_out`: optional int32 device scalar that receives the number zeroed.
+    zero_infinity=False: its loss is +inf and its gradient is not finite - NaN in the columns of its labels and of the
+    blank for t < input_length, exp(log_probs) * scale in the other columns (torch makes those NaN too), 0 beyond.
+    A target outside [0,V) (torch raises): loss NaN, gradient NaN for t < input_length and 0 beyond, with either setting.
+    Lengths are clamped as the kernels clamp them, input_lengths to T and target_lengths to targets.shape[1], the
+    'mean' divisor included.  The gradient comes back in the layout of log_probs: backed by a [B,T,V] tensor where
+    log_probs is the transposed view of one, a contiguous [T,B,V] otherwise."""
 
     @staticmethod
     def forward(ctx, log_probs, targets, input_lengths, target_lengths, blank, reduction, zero_infinity=False,
@@ -1313,7 +1319,7 @@ class CTCLossFn(Function):
         ctx.save_for_backward(log_probs, targets, il, tl, alpha, beta, lpg, nll)
         ctx.meta = (T, B, V, Lmax, blank, reduction, bool(zero_infinity))
         if reduction == "mean":
-            return (loss / tl.clamp(min=1).to(torch.float32)).mean()
+            return (loss / tl.clamp(min=1, max=max(Lmax, 1)).to(torch.float32)).mean()
         if reduction == "sum":
             return loss.sum()
         return loss
@@ -1325,7 +1331,7 @@ class CTCLossFn(Function):
         T, B, V, Lmax, blank, reduction, zero_infinity = ctx.meta
         dev = log_probs.device
         if reduction == "mean":
-            gscale = gout.to(torch.float32) / (tl.clamp(min=1).to(torch.float32) * B)
+            gscale = gout.to(torch.float32) / (tl.clamp(min=1, max=max(Lmax, 1)).to(torch.float32) * B)
         elif reduction == "sum":
             gscale = gout.to(torch.float32).expand(B)
         else:

@@ -1071,6 +1071,25 @@ int asrk_ctc_loss_bwd_f32(const float *lp, int64_t stride_t, int64_t stride_b, i
                           const float *nll, const float *gscale, float *grad, int64_t g_stride_t,
                           int64_t g_stride_b, void *stream);
 
+/* An utterance whose nll is NaN (a target outside [0,V), flagged by the forward without reading out of bounds) gets, from
+ * both bwd entry points and with any flags: NaN in every gradient element of its frames t < input_length[b], 0 beyond,
+ * and nothing written outside its own rows - its labels are never used as a column index.  The gradient norm of the
+ * batch is then NaN, which is what a solver's non-finite-gradient guard tests.
+ *
+ * What the two loss calls launch for a shape, from the planner the launchers themselves use; host only (no device call,
+ * runs without a GPU; tests/test_loss_plan_cpu.py holds the CTC case table of tests/loss_reference.py to it).
+ * ASRK_EINVAL: info == NULL, n < ASRK_CTC_LOSS_PLAN_INFO_LEN or a negative size; ASRK_ESHAPE: Lmax > 1023 (as the
+ * launches); info[0..n) is zeroed first whenever info and n are valid.  Otherwise ASRK_OK and
+ *   [0] the lattice kernel's states-per-lane template: 4 (up to 256 states), 16 (up to 1024) or 32
+ *   [1] its FAST flag: 1 = hardware exp / log (template 4 and T <= 512), 0 = library expf / logf
+ *   [2] spl = ceil((2*Lmax+1) / 64), the states each lane holds
+ *   [3] the gather grid's y = ceil(T / 8) (0: B == 0 or T == 0, no gather launch)
+ *   [4] the gradient kernel's t_per_block (frames per workgroup, a multiple of 4) and [5] its chunk count (grid y);
+ *       [4] x [5] >= T > [4] x ([5] - 1); both 0 where the backward launches nothing (B == 0 or T == 0)
+ *   [6] the dense gradient grid = ceil(T*B / 4)   [7] 2*Lmax+1 */
+#define ASRK_CTC_LOSS_PLAN_INFO_LEN 8
+int asrk_ctc_loss_plan_info(int T, int B, int Lmax, int *info, int n);
+
 /* The same two calls with flags; asrk_ctc_loss_{fwd,bwd}_f32 are these with flags = 0 (loss, n_infeasible NULL).
  * ASRK_CTC_ZERO_INFINITY = torch's zero_infinity=True.  An utterance whose targets have no path through its frames
  * has nll[b] = +inf, and nll keeps that value: it is the marker the backward tests.
