@@ -211,6 +211,57 @@ __device__ __forceinline__ void split3(float a, unsigned &b0, unsigned &b1, unsi
     b2 = __builtin_bit_cast(unsigned short, h2);
 }
 
+// One v_mfma_f32_16x16x32_bf16 whose A operand is a fragment of the register-resident W_hh slice.  hipcc parks those
+// fragments in the accumulator half of the register file and, through the builtin, copies four registers back
+// (v_accvgpr_read_b32) in front of every MFMA that uses them; the hardware reads MFMA A/B operands from AGPRs
+// directly.  The statement names no register: "a" asks for the resident operand in AGPRs, where it already lives, so
+// nothing writes it inside the time-step loop and it needs no wait state; the accumulator is taken whole as C by the
+// next MFMA of its chain (no wait state either).  Whatever else touches an accumulator after such a statement -
+// compiler code included - goes behind mfma_res_drain().  Fast paths only; -DASRK_REC_MFMA_BUILTIN keeps the builtin
+// form compilable for A/B runs.  Audit after every edit: tools/rec_isa_audit.py.
+__device__ __forceinline__ void mfma_res(f32x4 &acc, const bf16x8_t &a_res, const bf16x8_t &b) {
+#ifdef ASRK_REC_MFMA_BUILTIN
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_res, b, acc, 0, 0, 0);
+#else
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(a_res), "v"(b));
+#endif
+}
+// The same statement with the A operand in VGPRs (a fragment just read from LDS, or a resident one that did not fit
+// the accumulator file): for a chain that mixes both operand forms, so that its accumulator stays in one place and
+// hipcc has no copy to put between two MFMAs of the chain.
+__device__ __forceinline__ void mfma_reg(f32x4 &acc, const bf16x8_t &a, const bf16x8_t &b) {
+#ifdef ASRK_REC_MFMA_BUILTIN
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+#else
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+#endif
+}
+// Makes a resident fragment an accumulator-file value from its definition on, so that every "a" use below reads the
+// one copy; without it the allocator keeps a VGPR-class value and writes it INTO an AGPR in front of each statement.
+__device__ __forceinline__ void mfma_res_home(bf16x8_t &a_res) {
+#ifndef ASRK_REC_MFMA_BUILTIN
+    asm volatile("" : "+a"(a_res));
+#endif
+}
+// An accumulator's zero fill is a constant hipcc would re-create right in front of the first statement that takes it -
+// a just-written operand.  Behind this (empty) statement the value is opaque and stays where the fill put it.
+__device__ __forceinline__ void mfma_res_pin(f32x4 &acc) {
+#ifndef ASRK_REC_MFMA_BUILTIN
+    asm volatile("" : "+v"(acc));
+#endif
+}
+// An 8-pass MFMA's result may be touched by anything but the C operand of the next MFMA only 12 wait states after it
+// issued, and hipcc pads nothing for an asm statement: the states stand in this string.  Volatile statements keep
+// their order, so one wait (first = true) behind the last mfma_res covers every accumulator named after it.
+__device__ __forceinline__ void mfma_res_drain(f32x4 &acc, bool first) {
+#ifndef ASRK_REC_MFMA_BUILTIN
+    if (first)
+        asm volatile("s_nop 11" : "+v"(acc));
+    else
+        asm volatile("" : "+v"(acc));
+#endif
+}
+
 struct FwdPlan {
     int MT, NT, KGW, U, nwg, nbg, BG, HP, kgp, db;
     size_t lds, xfloats;

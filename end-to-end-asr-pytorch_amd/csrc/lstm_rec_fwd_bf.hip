@@ -31,6 +31,9 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_bf_kernel(RecFwdArgs p) {
     constexpr int CL = MT * NT * 64;
     constexpr int CW = CL / 4;
     constexpr int CPT = (CW + 63) / 64;
+    // 32-k steps whose register planes live in the accumulator half of the register file and feed the fast path's MFMAs
+    // from there; MT = 4 would fill all 256 AGPRs, so its last step stays in VGPRs
+    constexpr int JRA = MT == 4 ? KSW - 1 : KSW;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kq = wave;                         // K quarter of this wave (= its SIMD)
     const int ngroups = p.ndir * p.nbg;
@@ -75,8 +78,10 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_bf_kernel(RecFwdArgs p) {
                 for (int pl = 0; pl < 3; ++pl) {
                     if (pl < NLP)
                         *reinterpret_cast<u32x4 *>(Wl + ((size_t)((pl * MT + mt) * KS_TOT + g) * 64 + lane) * 16) = wp[pl];
-                    else
+                    else {
                         areg[mtl][j][pl - NLP] = __builtin_bit_cast(bf16x8_t, wp[pl]);
+                        if (j < JRA) mfma_res_home(areg[mtl][j][pl - NLP]);
+                    }
                 }
             }
         }
@@ -145,6 +150,11 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_bf_kernel(RecFwdArgs p) {
     }
 
     const unsigned char *a_lds = Wl + ((size_t)(kq * KSW) * 64 + lane) * 16;   // + (plane*MT + mt)*KS_TOT KiB + j KiB
+    // ds_read offsets are 16 bits and the slice is up to 128 KiB: one second base, opaque so that the fragments' addresses
+    // are these two registers + immediates and not a register each (which the wide plans reload from AGPRs in the loop)
+    static_assert(NLP * MT * 4 * KSW * 1024 <= 2 * 65536, "two bases cover the slice");
+    unsigned a_hi = 65536u;
+    asm volatile("" : "+v"(a_hi));
 
     for (int s = 0; s < p.T; ++s) {
         const int t = dir == 0 ? s : p.T - 1 - s;
@@ -152,37 +162,49 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_bf_kernel(RecFwdArgs p) {
 #pragma unroll
         for (int a = 0; a < MT; ++a)
 #pragma unroll
-            for (int b = 0; b < NT; ++b) acc[a][b][0] = acc[a][b][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < NT; ++b) {
+                acc[a][b][0] = acc[a][b][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                mfma_res_pin(acc[a][b][0]);
+                mfma_res_pin(acc[a][b][1]);
+            }
 
         // A fragments (planes 0, 1) of 32-k step j from LDS
         auto load_a = [&](bf16x8_t (&af)[MT][NLP], int j) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int pl = 0; pl < NLP; ++pl)
-                    af[mt][pl] = *reinterpret_cast<const bf16x8_t *>(
-                        a_lds + ((size_t)((pl * MT + mt) * KS_TOT + j)) * 1024);
+                for (int pl = 0; pl < NLP; ++pl) {
+                    const unsigned off = (unsigned)((pl * MT + mt) * KS_TOT + j) * 1024u;
+                    af[mt][pl] = *reinterpret_cast<const bf16x8_t *>(a_lds + (off >> 16 ? a_hi : 0u) + (off & 0xffffu));
+                }
         };
         // term g of one 32-k step (g = 0..5: the six partial products, small ones first): MT*NT MFMAs on
         // MT*NT different accumulator tiles; chains alternate between terms
-        auto term = [&](int g, int j, const bf16x8_t (&af)[MT][NLP], const u32x4 (&bfr)[NT][3]) {
+        // fast: every MFMA is an operand-form statement (mfma_res for planes resident in AGPRs, mfma_reg for the others),
+        // the caller drains the accumulators behind its last term
+        auto term = [&](int g, int j, const bf16x8_t (&af)[MT][NLP], const u32x4 (&bfr)[NT][3], bool fast) {
             const int pa = g == 0 ? 2 : (g == 1 || g == 3) ? 1 : 0;           // A plane: 2 1 0 1 0 0
             const int pb = g == 0 ? 0 : g == 1 ? 1 : g == 2 ? 2 : g == 3 ? 0 : g == 4 ? 1 : 0;   // B: 0 1 2 0 1 0
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[mt][nt][g & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        pa >= NLP ? areg[mt][j][pa >= NLP ? pa - NLP : 0] : af[mt][pa < NLP ? pa : 0],
-                        __builtin_bit_cast(bf16x8_t, bfr[nt][pb]),
-                        acc[mt][nt][g & 1], 0, 0, 0);
+                for (int nt = 0; nt < NT; ++nt) {
+                    const bf16x8_t &a = pa >= NLP ? areg[mt][j][pa >= NLP ? pa - NLP : 0] : af[mt][pa < NLP ? pa : 0];
+                    const bf16x8_t b = __builtin_bit_cast(bf16x8_t, bfr[nt][pb]);
+                    if (!fast)
+                        acc[mt][nt][g & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[mt][nt][g & 1], 0, 0, 0);
+                    else if (pa >= NLP && j < JRA)
+                        mfma_res(acc[mt][nt][g & 1], a, b);
+                    else
+                        mfma_reg(acc[mt][nt][g & 1], a, b);
+                }
         };
         // plain (not interleaved) 32-k step for the slow path
         auto kstep = [&](int j, const u32x4 (&bfr)[NT][3]) {
             bf16x8_t af[MT][NLP];
             load_a(af, j);
 #pragma unroll
-            for (int g = 0; g < 6; ++g) term(g, j, af, bfr);
+            for (int g = 0; g < 6; ++g) term(g, j, af, bfr, false);
         };
 
         REC_STAMP_W(0);
@@ -238,7 +260,7 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_bf_kernel(RecFwdArgs p) {
                     if (j + 1 < KSW) load_a(afr[(j + 1) & 1], j + 1);
 #pragma unroll
                     for (int g = 0; g < 6; ++g) {
-                        term(g, j, afr[j & 1], bf[j % RING]);
+                        term(g, j, afr[j & 1], bf[j % RING], true);
                         __builtin_amdgcn_sched_barrier(0);
                         constexpr int every = 6 / (NT * 3);         // 2 batch tiles: after every group, 1: every 2nd
                         if (j + PF < KSW && g % every == 0) {
@@ -249,6 +271,12 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_bf_kernel(RecFwdArgs p) {
                         }
                     }
                 }
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) mfma_res_drain(acc[mt][nt][c], mt + nt + c == 0);
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
