@@ -237,6 +237,12 @@ SIGNATURES = {
                            + [c_i64, c_vp]),
     "asrk_rnnt_greedy_step_f32": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                           c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_rnnt_joint_slots_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                          c_vp]),
+    "asrk_rnnt_beam_rows_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_f32, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_rnnt_beam_select": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_int]
+                              + [c_vp] * 16),
 }
 
 _lib = None

@@ -26,13 +26,17 @@ The optional block `decode: {transducer: {enable: true, max_symbols: 3, max_len_
 decoding with the RNN-transducer head (ASR.transducer_greedy; src/transducer.py) and writes the usual
 `..._output.csv`; the block never reaches the beam decoders.  The training config must have built the head (`model:
 transducer:`), otherwise the run stops with an error.  Without the block nothing here changes.
+With `beam_size: W` (> 1) or `lm_weight` (> 0) in the block the hypotheses come from the transducer beam search
+(ASR.transducer_beam: merged alignments, n-gram LM fusion from `decode.lm_path`, which must then be an ARPA / .ngram.npz
+file); `..._output.csv` receives the best hypothesis and, with `nbest` > 1, `..._beam-<W>-<lm_weight>.csv` lists every
+hypothesis with its score.  Otherwise the greedy search runs as before.
 """
 import os
 
 from . import align_asr, test_asr
 from ..parallel import gather_in_order
 from ..src.rescore import RescoreDecoder, check_decode_config
-from ..src.transducer import take_decode_block
+from ..src.transducer import take_decode_block, uses_beam
 
 
 class _FusedGreedy:
@@ -51,10 +55,11 @@ class Solver(test_asr.Solver):
     def __init__(self, config, paras, mode):
         self.align = bool(config['decode'].get('align', False))
         # taken out of the block like `rescore` below; enabled, the run takes the parent's greedy set-up (batch-wise
-        # loaders, one output file per set), whatever beam_size says: the transducer search here is greedy
+        # loaders, one output file per set), whatever decode.beam_size says: the transducer searches are batched and take
+        # their own beam_size from the block
         self.transducer = take_decode_block(config['decode'])
         if self.transducer:
-            config['decode']['beam_size'] = 1
+            config['decode']['beam_size'] = 1       # (the parent's; the transducer's own is self.transducer['beam_size'])
         check_decode_config(config['decode'], config.get('emb'))
         # taken out of the block: the parent hands the whole decode block to BeamDecoder(**dcfg)
         rescore = config['decode'].pop('rescore', None) or {}
@@ -81,6 +86,18 @@ class Solver(test_asr.Solver):
             self.decoder = self.model
             self.ctc_only = False
             self.enable_att = True  # (write_hyp: transducer hypotheses are never repeat-merged)
+            self.transducer_lm = None
+            if uses_beam(self.transducer):
+                opts = self.transducer
+                if opts.get('lm_weight', 0.0) > 0:
+                    from ..src.ngram import NGramLM
+                    self.transducer_lm = NGramLM.from_file(self.config['decode']['lm_path'],
+                                                           self.vocab_size).to(self.device)
+                self.verbose(['Decode spec| Transducer beam search \t| Beam size = {} | N-best = {} | LM weight = {} | '
+                              'Max symbols per frame = {} | Max len ratio = {}'.format(
+                                  opts.get('beam_size', 1), opts.get('nbest', 1), opts.get('lm_weight', 0.0),
+                                  opts['max_symbols'], opts['max_len_ratio'])])
+                return
             self.verbose(['Decode spec| Greedy transducer decoding \t| Max symbols per frame = {} | Max len ratio = {}'
                           .format(self.transducer['max_symbols'], self.transducer['max_len_ratio'])])
             return
@@ -130,6 +147,19 @@ class Solver(test_asr.Solver):
             i = batch_ids[k]
             self.progress('Valid step - {}/{}'.format(i + 1, len(dv_set)))
             feat, feat_len, txt, txt_len = self.fetch_data(data)
+            if uses_beam(self.transducer):
+                opts = self.transducer
+                tokens, n_tok, score, n_hyp, _ = self.model.transducer_beam(
+                    feat, feat_len, opts.get('beam_size', 1), opts['max_symbols'], opts['max_len_ratio'],
+                    nbest=opts.get('nbest', 1), lm=self.transducer_lm, lm_weight=opts.get('lm_weight', 0.0))
+                tokens, n_tok, score, n_hyp = tokens.tolist(), n_tok.tolist(), score.tolist(), n_hyp.tolist()
+                for j in range(len(txt)):
+                    idx = j + self.config['data']['corpus']['batch_size'] * i
+                    hyps = [tokens[j][h][:n_tok[j][h]] for h in range(n_hyp[j])]
+                    if opts.get('nbest', 1) > 1:         # the scores travel with the hypotheses to write_hyp
+                        hyps = [(hyp, score[j][h]) for h, hyp in enumerate(hyps)]
+                    results.append((str(idx), hyps, txt[j].tolist()))
+                continue
             tokens, n_tok, _ = self.model.transducer_greedy(feat, feat_len, self.transducer['max_symbols'],
                                                             self.transducer['max_len_ratio'])
             tokens, n_tok = tokens.tolist(), n_tok.tolist()      # one read-back per batch, after the search
@@ -137,6 +167,24 @@ class Solver(test_asr.Solver):
                 idx = j + self.config['data']['corpus']['batch_size'] * i
                 results.append((str(idx), [tokens[j][:n_tok[j]]], txt[j].tolist()))
         return results
+
+    def write_hyp(self, results, best_path, beam_path):
+        ''' the parent's files; the n-best lists of the transducer beam search go to the beam file as well, one row per
+            hypothesis with its score '''
+        opts = getattr(self, 'transducer', None)
+        if not (uses_beam(opts) and opts.get('nbest', 1) > 1):
+            return super().write_hyp(results, best_path, beam_path)
+        super().write_hyp([(name, [h[0] for h in hyps], truth) for name, hyps, truth in results], best_path, beam_path)
+        tail = '_output.csv'
+        assert best_path.endswith(tail)
+        nbest_path = best_path[:-len(tail)] + '_beam-{}-{}.csv'.format(opts.get('beam_size', 1), opts.get('lm_weight', 0.0))
+        with open(nbest_path, 'w', encoding='UTF-8') as f:
+            f.write('idx\tbeam\tscore\thyp\ttruth\n')
+            for name, hyps, truth in results:
+                ref = self.tokenizer.decode(truth)
+                for b, (hyp, score) in enumerate(hyps):
+                    f.write('\t'.join([name, str(b), repr(score), self.tokenizer.decode(hyp), ref]) + '\n')
+        self.verbose('N-best lists are stored at {}'.format(nbest_path))
 
     def exec(self):
         if getattr(self, 'align', False):      # (a solver assembled without __init__ decodes)

@@ -1723,6 +1723,105 @@ def rnnt_greedy_step(logits, enc_len, T, state, max_symbols, max_len, blank=0):
     return state
 
 
+# --------------------------------------------------------------------------- transducer beam search (csrc/rnnt_beam.hip)
+RNNT_BEAM_MAX = 32          # RB_MAX_BEAM of csrc/rnnt_beam.inc
+
+RNNTBeamState = collections.namedtuple(
+    "RNNTBeamState", ["B", "W", "K", "max_len", "n_live", "t_ptr", "n_sym", "n_tok", "score", "tokens", "fin_n",
+                      "fin_len", "fin_score", "fin_tok", "parent", "last_tok", "emit", "sel", "lm_sel", "lse", "lpb",
+                      "val", "lab"])
+
+
+def rnnt_beam_state(B, W, K, max_len, device):
+    """the device-resident bookkeeping of the beam search at its start: buffer 0 holds one live hypothesis per utterance
+    (empty sequence, frame 0, score 0), the finished lists are empty.  Every state array is double buffered [2, B, ...]."""
+    if not (1 <= W <= RNNT_BEAM_MAX and 1 <= K <= W and max_len >= 0):
+        raise _lib.AsrkError("rnnt_beam_state: 1 <= K <= W <= %d and max_len >= 0" % RNNT_BEAM_MAX)
+    Lc = max(int(max_len), 1)
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)   # noqa: E731
+    n_live = z((2, B), torch.int32)
+    n_live[0].fill_(1)
+    return RNNTBeamState(
+        B, W, K, int(max_len), n_live, z((2, B, W), torch.int32), z((2, B, W), torch.int32), z((2, B, W), torch.int32),
+        z((2, B, W), torch.float64), z((2, B, W, Lc), torch.int32), z((2, B), torch.int32), z((2, B, W), torch.int32),
+        z((2, B, W), torch.float64), z((2, B, W, Lc), torch.int32), z((B * W,), torch.int64), z((B * W,), torch.int64),
+        z((B * W,), torch.int32), z((B * W,), torch.int64), z((B * W,), torch.int64), z((B * W,), torch.float32),
+        z((B * W,), torch.float32), z((B * W, K), torch.float32), z((B * W, K), torch.int32))
+
+
+@torch.no_grad()
+def rnnt_joint_slots(E, P, t_ptr, W):
+    """the joint of the beam search: tanh(E[r // W, t_ptr[r]] + P[r]) -> [B*W, J]; E [B,T,J] is not repeated per slot,
+    P [B*W, J], t_ptr int32 [B*W] (clamped to the last frame by the kernel)"""
+    _require_gpu(E)
+    E, P = _f32c(E), _f32c(P)
+    B, T, J = E.shape
+    if P.shape != (B * W, J) or t_ptr.dtype != torch.int32 or t_ptr.numel() != B * W or not t_ptr.is_contiguous():
+        raise _lib.AsrkError("rnnt_joint_slots: P must be [B*W, J] and t_ptr int32 [B*W]")
+    H = torch.empty((B * W, J), dtype=torch.float32, device=E.device)
+    _lib.check(_L().asrk_rnnt_joint_slots_f32(_p(E), J, _p(P), J, _p(t_ptr), B, T, W, J, _p(H), J, _stream()),
+               "rnnt_joint_slots")
+    return H
+
+
+@torch.no_grad()
+def rnnt_beam_rows(logits, W, K, lm=None, lm_weight=0.0, n_live=None, blank=0, out=None):
+    """row pass of the beam search (asrk_rnnt_beam_rows_f32) on logits [B*W, V] (a row-strided 2-d view is taken as it
+    is) and optional LM log-probabilities [B*W, V] -> (lse [B*W], lpb [B*W], val [B*W, K], lab int32 [B*W, K]);
+    n_live int32 [B]: rows w >= n_live[b] are not read"""
+    _require_gpu(logits)
+    x = logits
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        x = _f32c(logits)
+    M, V = x.shape
+    if M % W:
+        raise _lib.AsrkError("rnnt_beam_rows: the logits must hold B*W rows")
+    l, ldl = None, 0
+    if lm is not None:
+        l = lm if (lm.dtype == torch.float32 and lm.dim() == 2 and lm.stride(1) == 1) else _f32c(lm).view(M, -1)
+        if l.shape != (M, V):
+            raise _lib.AsrkError("rnnt_beam_rows: the LM rows must be [B*W, V]")
+        ldl = l.stride(0)
+    if n_live is not None and (n_live.dtype != torch.int32 or n_live.numel() != M // W or not n_live.is_contiguous()):
+        raise _lib.AsrkError("rnnt_beam_rows: n_live must be int32 [B]")
+    if out is None:
+        dev = x.device
+        out = (torch.empty((M,), dtype=torch.float32, device=dev), torch.empty((M,), dtype=torch.float32, device=dev),
+               torch.empty((M, K), dtype=torch.float32, device=dev), torch.empty((M, K), dtype=torch.int32, device=dev))
+    lse, lpb, val, lab = out
+    _lib.check(_L().asrk_rnnt_beam_rows_f32(_p(x), x.stride(0), _p(l), ldl, float(lm_weight), _p(n_live), M // W, W, V,
+                                            K, blank, _p(lse), _p(lpb), _p(val), _p(lab), _stream()), "rnnt_beam_rows")
+    return out
+
+
+@torch.no_grad()
+def rnnt_beam_select(state, enc_len, T, max_symbols, cur):
+    """one select step (asrk_rnnt_beam_select) on the table state.lpb / val / lab: reads beam buffer `cur`, writes the
+    other one and the gather indices; nothing is read back.  enc_len int64 [B] on the device."""
+    s = state
+    _require_gpu(s.score)
+    R, Lc = s.B * s.W, s.tokens.shape[3]
+    want = [(s.n_live, torch.int32, (2, s.B)), (s.t_ptr, torch.int32, (2, s.B, s.W)),
+            (s.n_sym, torch.int32, (2, s.B, s.W)), (s.n_tok, torch.int32, (2, s.B, s.W)),
+            (s.score, torch.float64, (2, s.B, s.W)), (s.tokens, torch.int32, (2, s.B, s.W, Lc)),
+            (s.fin_n, torch.int32, (2, s.B)), (s.fin_len, torch.int32, (2, s.B, s.W)),
+            (s.fin_score, torch.float64, (2, s.B, s.W)), (s.fin_tok, torch.int32, (2, s.B, s.W, Lc)),
+            (s.parent, torch.int64, (R,)), (s.last_tok, torch.int64, (R,)), (s.emit, torch.int32, (R,)),
+            (s.sel, torch.int64, (R,)), (s.lm_sel, torch.int64, (R,)), (s.lpb, torch.float32, (R,)),
+            (s.val, torch.float32, (R, s.K)), (s.lab, torch.int32, (R, s.K)), (enc_len, torch.int64, (s.B,))]
+    for t, dt, shape in want:
+        if (not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
+                or t.device != s.score.device):
+            raise _lib.AsrkError("rnnt_beam_select: state, table and enc_len must be contiguous device tensors of the "
+                                 "shapes and types of rnnt_beam_state (enc_len int64 [B])")
+    _lib.check(_L().asrk_rnnt_beam_select(
+        _p(s.lpb), _p(s.val), _p(s.lab), _p(enc_len), s.B, T, s.W, s.K, max_symbols, s.max_len, s.tokens.shape[3],
+        int(cur), _p(s.n_live), _p(s.t_ptr), _p(s.n_sym), _p(s.n_tok), _p(s.score), _p(s.tokens), _p(s.fin_n),
+        _p(s.fin_len), _p(s.fin_score), _p(s.fin_tok), _p(s.parent), _p(s.last_tok), _p(s.emit), _p(s.sel),
+        _p(s.lm_sel), _stream()), "rnnt_beam_select")
+    return state
+
+
 # --------------------------------------------------------------------------- cross entropy
 def _check_label_smoothing(eps):
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:

@@ -106,6 +106,20 @@ class ASR(nn.Module):
         return tokens, n_tok, encode_len
 
     @torch.no_grad()
+    def transducer_beam(self, audio_feature, feature_len, beam_size, max_symbols=3, max_len_ratio=0.5, nbest=1, lm=None,
+                        lm_weight=0.0):
+        ''' batched transducer beam search with merged alignments and optional n-gram LM fusion: encoder ->
+            TransducerHead.beam_search, the limits as in transducer_greedy.  Returns (tokens int64 [B, nbest, max_len]
+            zero-padded, n_tokens int32 [B, nbest], score float64 [B, nbest], n_hyp int32 [B], encode_len [B]), best
+            hypothesis first, all on the device '''
+        self._need_transducer('transducer_beam')
+        encode_feature, encode_len = self.encoder(audio_feature, feature_len)
+        max_len = max(1, int(np.ceil(encode_feature.shape[1] * float(max_len_ratio))))
+        tokens, n_tok, score, n_hyp = self.transducer.beam_search(encode_feature, encode_len, beam_size, max_symbols,
+                                                                  max_len, nbest=nbest, lm=lm, lm_weight=lm_weight)
+        return tokens, n_tok, score, n_hyp, encode_len
+
+    @torch.no_grad()
     def ctc_align(self, audio_feature, feature_len, txt, txt_len, packed=False):
         ''' Forced alignment of every utterance to its transcript with the CTC head: encoder -> CTC head ->
             log_softmax -> ops.ctc_align (the best CTC path, found and traced back on the device).  txt [B,L] padded

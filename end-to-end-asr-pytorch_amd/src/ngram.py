@@ -251,10 +251,11 @@ class NGramLM(nn.Module):
             self.order, self.img_bo.numel(), self.img_word.numel())]
 
     # ---- the step ----------------------------------------------------------------------------------------------
-    def forward(self, x, lens=None, hidden=None, parent=None):
+    def forward(self, x, lens=None, hidden=None, parent=None, out=None, state_out=None):
         ''' x [B,1] int64 token ids, hidden None (every row starts from the empty context) or the int32 state
             [1,rows,1] of an earlier call, parent None or [B] int32 / int64 (row r continues hidden[parent[r]]: the
-            survivors' gather folded into the launch) -> (logp [B,1,V] float32, state [1,B,1] int32) '''
+            survivors' gather folded into the launch) -> (logp [B,1,V] float32, state [1,B,1] int32).
+            out / state_out: contiguous float32 [B*V] / int32 [B] storage of the caller's to write them into '''
         from .. import _lib, ops
         dev = self.img_bo.device
         if dev.type != 'cuda':
@@ -272,8 +273,16 @@ class NGramLM(nn.Module):
                 par, par64 = parent.to(dev).contiguous(), int(parent.dtype == torch.int64)
             else:
                 assert n_state == B
-        out = torch.empty((B, 1, self.vocab_size), dtype=torch.float32, device=dev)
-        state = torch.empty((1, B, 1), dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty((B, 1, self.vocab_size), dtype=torch.float32, device=dev)
+        else:
+            assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * self.vocab_size
+            out = out.view(B, 1, self.vocab_size)
+        if state_out is None:
+            state = torch.empty((1, B, 1), dtype=torch.int32, device=dev)
+        else:
+            assert state_out.dtype == torch.int32 and state_out.is_contiguous() and state_out.numel() == B
+            state = state_out.view(1, B, 1)
         p = ops._p
         _lib.check(_lib.load().asrk_ngram_step_f32(
             self.order, self.vocab_size, self.img_bo.numel(), self.img_word.numel(), p(self.img_uni_logp),

@@ -1,6 +1,7 @@
 """RNN-transducer head (Graves 2012) on the pyramidal encoder: embedding + unidirectional LSTM/GRU prediction network,
 joint network tanh(lin_enc(enc)[b,t] + lin_pred(pred)[b,u]) -> lin_out -> [B, T', U+1, V] logits for ops.RNNTLoss, and
-batched greedy decoding with device-resident bookkeeping (csrc/rnnt.hip).  Blank = <sos> = 0.
+batched greedy decoding with device-resident bookkeeping (csrc/rnnt.hip) and an alignment-length-synchronous beam search
+with merged alignments and n-gram LM fusion (csrc/rnnt_beam.hip).  Blank = <sos> = 0.
 """
 import torch
 import torch.nn as nn
@@ -31,13 +32,18 @@ def check_exclusive(config):
         raise ValueError('config blocks `model: transducer:` and `emb:` cannot be combined')
 
 
+BEAM_KEYS = ('beam_size', 'nbest', 'lm_weight')
+
+
 def take_decode_block(dcfg):
     ''' removes `transducer` from the decode block (the parent solver hands the rest to the beam decoders) and returns
-        {max_symbols, max_len_ratio} when it is enabled, else None '''
+        {max_symbols, max_len_ratio} when it is enabled, else None.  The beam-search keys beam_size (1..32), nbest
+        (1..beam_size) and lm_weight (>= 0) are validated and returned only when the block names them: beam_size > 1 or
+        lm_weight > 0 selects ASR.transducer_beam, and lm_weight > 0 needs an n-gram `decode.lm_path`. '''
     block = dcfg.pop('transducer', None) or {}
     if not isinstance(block, dict):
         raise ValueError('decode.transducer: expected a mapping, got %r' % (block,))
-    unknown = sorted(set(block) - {'enable', 'max_symbols', 'max_len_ratio'}, key=str)
+    unknown = sorted(set(block) - {'enable', 'max_symbols', 'max_len_ratio'} - set(BEAM_KEYS), key=str)
     if unknown:
         raise ValueError('decode.transducer: unknown key(s) {}'.format(unknown))
     if not block.get('enable', False):
@@ -47,7 +53,32 @@ def take_decode_block(dcfg):
     opts = {'max_symbols': int(block.get('max_symbols', 3)), 'max_len_ratio': float(block.get('max_len_ratio', 0.5))}
     if opts['max_symbols'] < 1 or not opts['max_len_ratio'] > 0:
         raise ValueError('decode.transducer: max_symbols must be >= 1 and max_len_ratio > 0')
+    for key in BEAM_KEYS:
+        if key in block:
+            v = block[key]
+            ok = not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float('inf')
+            if not ok or (key != 'lm_weight' and v != int(v)):
+                raise ValueError('decode.transducer: {} must be a {}, got {!r}'.format(
+                    key, 'finite number' if key == 'lm_weight' else 'whole number', v))
+            opts[key] = float(v) if key == 'lm_weight' else int(v)
+    beam_size = opts.get('beam_size', 1)
+    if not 1 <= beam_size <= 32:
+        raise ValueError('decode.transducer: beam_size must be in 1..32, got {}'.format(beam_size))
+    if not 1 <= opts.get('nbest', 1) <= beam_size:
+        raise ValueError('decode.transducer: nbest must be in 1..beam_size, got {}'.format(opts['nbest']))
+    if not opts.get('lm_weight', 0.0) >= 0:
+        raise ValueError('decode.transducer: lm_weight must be >= 0, got {}'.format(opts['lm_weight']))
+    if opts.get('lm_weight', 0.0) > 0:
+        from .ngram import is_ngram_path
+        if not is_ngram_path(dcfg.get('lm_path')):
+            raise ValueError('decode.transducer: lm_weight > 0 fuses an n-gram LM only: decode.lm_path must end in '
+                             '.arpa, .arpa.gz or .ngram.npz, got {!r}'.format(dcfg.get('lm_path')))
     return opts
+
+
+def uses_beam(opts):
+    ''' the decode block (take_decode_block's result) asks for the beam search rather than the greedy one '''
+    return bool(opts) and (opts.get('beam_size', 1) > 1 or opts.get('lm_weight', 0.0) > 0)
 
 
 class TransducerHead(nn.Module):
@@ -161,5 +192,117 @@ class TransducerHead(nn.Module):
     def _select(src, dst, parent, widths):
         ''' dst slot 0 [b] = src slot (parent[b] // B) [b] for every kept tensor, 8 segments per launch '''
         segs = [(s, d[0], w, 1, False) for s, d, w in zip(src, dst, widths)]
+        for i in range(0, len(segs), 8):
+            dops.gather_rows_multi(segs[i:i + 8], parent)
+
+    @torch.no_grad()
+    def beam_search(self, encode_feature, encode_len, beam_size, max_symbols, max_len, nbest=1, lm=None, lm_weight=0.0):
+        ''' alignment-length-synchronous beam search (Saon et al. 2020) in lock-step over the batch, W = beam_size slots
+            per utterance (rows r = b * W + w) -> (tokens int64 [B, nbest, max_len] zero-padded, n_tok int32 [B, nbest],
+            score float64 [B, nbest] = ln of the summed probability of the kept alignments (+ lm_weight * LM), n_hyp
+            int32 [B]), best first, all on the device.  Each of the T' + max_len iterations runs the joint at every
+            row's own frame, lin_out, one row pass (log-sum-exp, blank, the K = min(W, V - 1) best labels by
+            lp + lm_weight * lm; csrc/rnnt_beam.hip) and one select launch (candidates, merge of equal sequences, cut to
+            W, finished list); then the survivors' states are gathered from their parents, the cells, lin_pred and the
+            LM step on the appended token, and the stepped state is kept where a token was appended.  Nothing is read
+            back inside the loop.  lm: an NGramLM (its log-probabilities are added to the labels, never to blank). '''
+        nbest, max_len = int(nbest), int(max_len)
+        if not 1 <= nbest <= int(beam_size):
+            raise ValueError('beam_search: 1 <= nbest <= beam_size, got nbest = {}'.format(nbest))
+        st = None
+        for _, st in self.beam_steps(encode_feature, encode_len, beam_size, max_symbols, max_len, lm, lm_weight):
+            pass
+        dev = encode_feature.device
+        B, T, _ = encode_feature.shape
+        f = (T + max_len) & 1                       # the buffer the last iteration wrote
+        tokens = torch.zeros((B, nbest, max_len), dtype=torch.int64, device=dev)
+        n_tok = st.fin_len[f][:, :nbest].clone()
+        valid = torch.arange(nbest, device=dev).view(1, nbest) < st.fin_n[f].view(B, 1)
+        n_tok = torch.where(valid, n_tok, torch.zeros_like(n_tok))
+        if max_len > 0:
+            pos = torch.arange(max_len, device=dev).view(1, 1, max_len)
+            tokens = torch.where(pos < n_tok.unsqueeze(2), st.fin_tok[f][:, :nbest, :max_len].to(torch.int64), tokens)
+        score = torch.where(valid, st.fin_score[f][:, :nbest], torch.full_like(st.fin_score[f][:, :nbest], float('-inf')))
+        return tokens, n_tok, score, torch.clamp(st.fin_n[f], max=nbest)
+
+    @torch.no_grad()
+    def beam_steps(self, encode_feature, encode_len, beam_size, max_symbols, max_len, lm=None, lm_weight=0.0):
+        ''' the loop of beam_search as a generator: yields (i, state) after iteration i = 0 .. T' + max_len - 1, `state`
+            the ops.RNNTBeamState whose buffer 1 - (i & 1) iteration i has just written (the next beam and the finished
+            list so far).  Nothing is read back; a caller that stops early leaves the search unfinished. '''
+        from .ngram import NGramLM
+        if lm is not None and not isinstance(lm, NGramLM):
+            raise NotImplementedError('TransducerHead.beam_search fuses an NGramLM only, got {}'.format(
+                type(lm).__name__))
+        dev = encode_feature.device
+        B, T, _ = encode_feature.shape
+        W, max_symbols, max_len = int(beam_size), int(max_symbols), int(max_len)
+        if not 1 <= W <= ops.RNNT_BEAM_MAX or max_symbols < 0 or max_len < 0:
+            raise ValueError('beam_search: 1 <= beam_size <= {}, max_symbols >= 0, max_len >= 0'.format(
+                ops.RNNT_BEAM_MAX))
+        V = self.vocab_size
+        if lm is not None and lm.vocab_size != V:
+            raise ValueError('beam_search: the LM has {} tokens, the head {}'.format(lm.vocab_size, V))
+        use_lm = lm is not None and float(lm_weight) > 0
+        K = min(W, V - 1)
+        R = B * W
+        enc_len = torch.as_tensor(encode_len).to(device=dev, dtype=torch.int64).contiguous()
+        E = ops.linear(encode_feature, self.lin_enc.weight, self.lin_enc.bias)
+        st = ops.rnnt_beam_state(B, W, K, max_len, dev)
+        lstm = self.rnn_type == 'LSTM'
+        n_state = self.layer * (2 if lstm else 1)
+        widths = [self.dim] * n_state + [self.joint_dim]
+        # kept[x][0] = the kept value of every row; work[x] = [gathered from the parents, stepped on the appended token]
+        kept = [torch.zeros((2, R, w), dtype=torch.float32, device=dev) for w in widths]
+        work = [torch.zeros((2, R, w), dtype=torch.float32, device=dev) for w in widths]
+        ar = torch.arange(R, dtype=torch.int64, device=dev)
+
+        def step_cells(cur, tok):
+            ''' slot 1 of `cur` from slot 0 and the token `tok` [R] '''
+            inp = dops.embedding(tok, self.emb.weight)
+            for l in range(self.layer):
+                if lstm:
+                    hb, cb = cur[2 * l], cur[2 * l + 1]
+                    dops.lstm_cell_infer(inp, hb[0], cb[0], *self.pred.layer_params(l), out=(hb[1], cb[1]))
+                    inp = hb[1]
+                else:
+                    ops.copy_flat(cur[l][1], gru_ops.gru_cell_infer(inp, cur[l][0], *self.pred.layer_params(l)))
+                    inp = cur[l][1]
+            ops.copy_flat(cur[-1][1], ops.linear(inp, self.lin_pred.weight, self.lin_pred.bias))
+
+        # <sos> from the zero state is every row's first kept state
+        step_cells(work, st.last_tok)
+        self._select(work, kept, ar + R, widths)
+        if use_lm:
+            # LM rows and the int32 LM state (moved as 4-byte rows): [kept | stepped], two such buffers in turn
+            lm_rows = [torch.zeros((2, R, V), dtype=torch.float32, device=dev) for _ in range(2)]
+            lm_state = [torch.zeros((2, R, 1), dtype=torch.float32, device=dev) for _ in range(2)]
+            lm(st.last_tok.view(R, 1), None, None, out=lm_rows[0][0], state_out=lm_state[0][0].view(torch.int32))
+        table = (st.lse, st.lpb, st.val, st.lab)
+        k = 0
+        for i in range(T + max_len):
+            cur = i & 1
+            H = ops.rnnt_joint_slots(E, kept[-1][0], st.t_ptr[cur].view(-1), W)
+            logits = ops.linear(H, self.lin_out.weight, self.lin_out.bias)
+            ops.rnnt_beam_rows(logits, W, K, lm_rows[k][0] if use_lm else None, lm_weight if use_lm else 0.0,
+                               st.n_live[cur], self.blank, out=table)
+            ops.rnnt_beam_select(st, enc_len, T, max_symbols, cur)
+            # every row continues its parent: gather the kept states, step them on the appended token, keep the step
+            # where a token was appended
+            self._gather(kept, work, st.parent, widths)
+            step_cells(work, st.last_tok)
+            self._select(work, kept, st.sel, widths)
+            if use_lm:
+                lm(st.last_tok.view(R, 1), None, lm_state[k][0].view(torch.int32), parent=st.parent,
+                   out=lm_rows[k][1], state_out=lm_state[k][1].view(torch.int32))
+                dops.gather_rows_multi([(lm_rows[k], lm_rows[1 - k][0], V, 1, False),
+                                        (lm_state[k], lm_state[1 - k][0], 1, 1, False)], st.lm_sel)
+                k = 1 - k
+            yield i, st
+
+    @staticmethod
+    def _gather(src, dst, parent, widths):
+        ''' dst slot 0 [r] = src slot 0 [parent[r]] for every kept tensor, 8 segments per launch '''
+        segs = [(s[0], d[0], w, 1, False) for s, d, w in zip(src, dst, widths)]
         for i in range(0, len(segs), 8):
             dops.gather_rows_multi(segs[i:i + 8], parent)

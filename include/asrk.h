@@ -1275,6 +1275,40 @@ int asrk_rnnt_greedy_step_f32(const float *logits, int64_t ld, const int64_t *en
                               int64_t *tokens, int64_t tok_stride, int64_t *last_tok, int32_t *emit, int32_t *done,
                               void *stream);
 
+/* ---- transducer beam search (csrc/rnnt_beam.hip, csrc/rnnt_beam.inc; TransducerHead.beam_search) -----------------------
+ * Alignment-length-synchronous search, B utterances in lock-step with W <= 32 slots each; row r = b*W + w of every
+ * [B*W, ...] array.  The beam state is double buffered: arrays [2, B, ...], buffer `cur` is read and the other written.
+ *
+ * Joint step with several slots per utterance: H[r,:] = tanh(E[r / W, t_ptr[r], :] + P[r,:]); E [B,T,J] is not repeated
+ * per slot, t_ptr int32 [B*W] is clamped to [0, T-1].  Call site: ops.rnnt_joint_slots. */
+int asrk_rnnt_joint_slots_f32(const float *E, int64_t lde, const float *P, int64_t ldp, const int32_t *t_ptr, int B,
+                              int T, int W, int J, float *H, int64_t ldh, void *stream);
+/* Row pass over the logits z [B*W, V] (row stride ldz) and, with lm != NULL, the LM log-probabilities [B*W, V] (row
+ * stride ldlm): per row lse = logsumexp(z), lpb = z[blank] - lse and the K <= min(32, V-1) best labels k != blank by
+ * z[k] + lm_weight*lm[k] (the lower k among equal values), written as lab [B*W, K] int32 and
+ * val = (z[k] - lse) + lm_weight*lm[k] (z[k] - lse without an LM), descending.  A label whose ranking value is -inf or
+ * NaN is no candidate; missing entries are lab = -1, val = -inf.  The row is read once and held in registers: one wave
+ * per row below V = 2048, a 256-thread workgroup from there on, 16-byte loads when bases and strides allow;
+ * ASRK_ESHAPE above V = 16384.  Row w of utterance b with w >= n_live[b] (n_live int32 [B]; NULL: every row is live)
+ * is not read: lse = lpb = 0 and K padded entries.  Call site: ops.rnnt_beam_rows. */
+int asrk_rnnt_beam_rows_f32(const float *z, int64_t ldz, const float *lm, int64_t ldlm, float lm_weight,
+                            const int32_t *n_live, int B, int W, int V, int K, int blank, float *lse, float *lpb,
+                            float *val, int32_t *lab, void *stream);
+/* Select, one workgroup per utterance (rules and phases: csrc/rnnt_beam.inc): from the [W, K+1] table of the row pass
+ * and beam buffer `cur` it forms the candidates (blank first, then the labels of a slot with n_sym < max_symbols and
+ * n_tok < max_len), merges equal sequences (float64 logaddexp), keeps the W best, moves survivors with t_ptr == T_b to
+ * the finished list (capacity W, sorted by score, the earlier entry first on ties) and writes the other buffer:
+ * n_live int32 [2,B]; t_ptr, n_sym, n_tok int32 [2,B,W]; score float64 [2,B,W]; tokens int32 [2,B,W,tok_stride]
+ * (tok_stride >= max(max_len, 1)); fin_n int32 [2,B]; fin_len int32, fin_score float64 [2,B,W]; fin_tok as tokens.
+ * Live rows are packed in rank order.  Per row of the next beam it also writes what drives the caller's gathers:
+ * parent int64 (global row continued), last_tok int64 (label appended, else 0), emit int32, sel int64 = r + emit*B*W and
+ * lm_sel int64 = emit ? B*W + r : parent (dead rows: identity).  Nothing is read back.  Call site: ops.rnnt_beam_select. */
+int asrk_rnnt_beam_select(const float *lpb, const float *val, const int32_t *lab, const int64_t *enc_len, int B, int T,
+                          int W, int K, int max_symbols, int max_len, int64_t tok_stride, int cur, int32_t *n_live,
+                          int32_t *t_ptr, int32_t *n_sym, int32_t *n_tok, double *score, int32_t *tokens,
+                          int32_t *fin_n, int32_t *fin_len, double *fin_score, int32_t *fin_tok, int64_t *parent,
+                          int64_t *last_tok, int32_t *emit, int64_t *sel, int64_t *lm_sel, void *stream);
+
 /* ---- CTC prefix scores for joint CTC-attention beam search (src/ctc.py:76-116) -----------
  * All (hypothesis h, candidate c) pairs of one beam step in one launch.  x [T,V] log-probs;
  * r_prev [n,T,2] (0 = non-blank, 1 = blank path) of each hypothesis' prefix g_h; prefix_len[h] =
