@@ -243,6 +243,21 @@ SIGNATURES = {
                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
     "asrk_rnnt_beam_select": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_int]
                               + [c_vp] * 16),
+    "asrk_rnnt_simple_rows_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                          c_int, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_rnnt_simple_occ_f32": (c_int, [c_vp] * 7 + [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_rnnt_simple_grad_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                          c_int] + [c_vp] * 5 + [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "asrk_rnnt_prune_ranges_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "asrk_rnnt_joint_band_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64,
+                                         c_vp]),
+    "asrk_rnnt_joint_band_bwd_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                             c_i64, c_vp, c_i64, c_vp]),
+    "asrk_rnnt_rows_band_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_vp, c_vp, c_vp, c_vp]),
+    "asrk_rnnt_band_scatter_f32": (c_int, [c_vp] * 5 + [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "asrk_rnnt_grad_band_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                        c_int] + [c_vp] * 8 + [c_i64, c_vp]),
 }
 
 _lib = None

@@ -157,6 +157,7 @@ class Solver(BaseSolver):
         ''' Training End-to-end ASR system '''
         self.verbose('Total training steps {}.'.format(human_format(self.max_step)))
         ctc_loss, att_loss, emb_loss, rnnt_loss = None, None, None, None
+        rnnt_pruned, rnnt_simple = None, None
         n_epochs = 0
         self.timer.set()
         while self.step < self.max_step:
@@ -215,9 +216,14 @@ class Solver(BaseSolver):
                     if self.rnnt_on:
                         # a mean over utterances like CTC: the utterance-count weight under data parallel.  The loss's
                         # backward writes the gradient over the logits (nothing else reads them)
-                        logits = self.model.transducer_logits(encoded[0], encode_len, txt, txt_len)
-                        rnnt_loss = self.rnnt_loss(logits, txt, encode_len, txt_len, consume_logits=True)
-                        del logits
+                        if self.model.rnnt_prune is not None:
+                            # pruned training: the band loss plus simple_weight times the simple joiner's
+                            rnnt_loss, rnnt_pruned, rnnt_simple = \
+                                self.model.transducer_loss_pruned(encoded[0], encode_len, txt, txt_len)
+                        else:
+                            logits = self.model.transducer_logits(encoded[0], encode_len, txt, txt_len)
+                            rnnt_loss = self.rnnt_loss(logits, txt, encode_len, txt_len, consume_logits=True)
+                            del logits
                         shown_loss = shown_loss + rnnt_loss.detach() * self.model.rnnt_weight
                         total_loss = total_loss + \
                             (rnnt_loss if self.w_utt is None else rnnt_loss * self.w_utt) * self.model.rnnt_weight
@@ -238,7 +244,8 @@ class Solver(BaseSolver):
                 if (self.step == 1) or (self.step % self.PROGRESS_STEP == 0):
                     self.progress('Tr stat | Loss - {:.2f} | Grad. Norm - {:.2f} | {}'
                                   .format(shown_loss.detach().cpu().item(), float(grad_norm), self.timer.show()))
-                    self.write_log('loss', {'tr_ctc': ctc_loss, 'tr_att': att_loss, 'tr_rnnt': rnnt_loss})
+                    self.write_log('loss', {'tr_ctc': ctc_loss, 'tr_att': att_loss, 'tr_rnnt': rnnt_loss,
+                                            'tr_rnnt_pruned': rnnt_pruned, 'tr_rnnt_simple': rnnt_simple})
                     if mwer_on:
                         self.write_log('mwer', {'tr_exp_err': mwer_stats['exp_err'],
                                                 'tr_1best_err': mwer_stats['best_err']})

@@ -11,64 +11,12 @@
 //
 // The logits are read twice and written once; no [M, V] log_softmax exists at any time.  wave64, no float atomics:
 // every result is a pure function of its inputs, reproducible bit for bit.
-#include "common.h"
-
-#define RNNT_HD __device__
-#include "rnnt.inc"
+#include "rnnt_rows.h"
 
 namespace {
 
-constexpr int RNNT_WG_MIN_V = 2048;     // the case split of seq_logp (rescore.hip): a workgroup per row from here on
 constexpr int RNNT_LAT_THREADS = 128;   // lanes per direction of the lattice walk
 constexpr int RNNT_MAX_U1 = 2048;       // 4 diagonals of U1 floats in LDS: 32 KiB
-
-static inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// ---------------------------------------------------------------------------------------------
-// row reductions: running (max, sum of exp(x - max)) per lane, the arithmetic of seq_logp (rescore.hip)
-
-struct MaxSum {
-    float m, s;
-};
-
-__device__ __forceinline__ void ms_add(MaxSum &a, float v) {
-    if (v > a.m) {
-        a.s = a.s * expf(a.m - v) + 1.f;   // a.m == -inf: a.s is 0 and exp(-inf) = 0
-        a.m = v;
-    } else if (!(v == -INFINITY)) {
-        a.s += expf(v - a.m);              // NaN propagates
-    }
-}
-
-__device__ __forceinline__ void ms_add4(MaxSum &a, const f32x4 v) {
-    const float cm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-    if (cm > a.m) {
-        a.s *= expf(a.m - cm);
-        a.m = cm;
-    }
-    if (a.m > -INFINITY) a.s += expf(v[0] - a.m) + expf(v[1] - a.m) + expf(v[2] - a.m) + expf(v[3] - a.m);
-}
-
-__device__ __forceinline__ MaxSum ms_wave(MaxSum a) {
-    const float M = wave_max(a.m);
-    const float s = (a.m == -INFINITY) ? 0.f : a.s * expf(a.m - M);
-    return MaxSum{M, wave_sum(s)};
-}
-
-template <bool VEC>
-__device__ __forceinline__ MaxSum ms_row(const float *__restrict__ xr, int V, int tid, int nthreads) {
-    MaxSum a{-INFINITY, 0.f};
-    if (VEC) {
-        const int nv = V >> 2;
-#pragma unroll 4
-        for (int i = tid; i < nv; i += nthreads) ms_add4(a, reinterpret_cast<const f32x4 *>(xr)[i]);
-        for (int i = (nv << 2) + tid; i < V; i += nthreads) ms_add(a, xr[i]);
-    } else {
-#pragma unroll 4
-        for (int i = tid; i < V; i += nthreads) ms_add(a, xr[i]);
-    }
-    return a;
-}
 
 // row m = (b * T + t) * U1 + u of utterance b; false: the cell lies outside the utterance's lattice
 struct RowArgs {
@@ -163,13 +111,6 @@ __global__ __launch_bounds__(2 * RNNT_LAT_THREADS) void rnnt_lattice_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // gradient
-
-__device__ __forceinline__ float grad_value(float x, float lse, const RnntCoef &k, float gs, bool isb, bool isl) {
-    float g = expf((x - lse) + k.c);
-    if (isb) g -= k.eb;
-    if (isl) g -= k.el;
-    return gs * g;
-}
 
 struct GradArgs {
     const float *lse, *lpb, *lpl, *alpha, *beta, *nll, *gscale;

@@ -1822,6 +1822,208 @@ def rnnt_beam_select(state, enc_len, T, max_symbols, cur):
     return state
 
 
+# --------------------------------------------------------------------------- pruned transducer training (csrc/rnnt_prune.hip)
+RNNT_PRUNE_MAX_RANGE = 32   # PRUNE_MAX_S of csrc/rnnt_prune.hip
+
+
+def _rnnt_lengths(what, targets, enc_len, txt_len, B, U1, dev):
+    txt = torch.as_tensor(targets).to(device=dev, dtype=torch.int64)
+    if txt.dim() != 2 or txt.shape[0] != B or txt.shape[1] < U1 - 1:
+        raise _lib.AsrkError(what + ": targets must be [B, L] with L >= U")
+    el = torch.as_tensor(enc_len).to(device=dev, dtype=torch.int64).contiguous()
+    tl = torch.as_tensor(txt_len).to(device=dev, dtype=torch.int64).contiguous()
+    if el.numel() != B or tl.numel() != B:
+        raise _lib.AsrkError(what + ": one enc_len and one txt_len per utterance")
+    return txt.contiguous(), el, tl
+
+
+def _band_starts(what, s, B, T, dev):
+    if not torch.is_tensor(s) or s.dtype != torch.int32 or tuple(s.shape) != (B, T) or s.device != dev:
+        raise _lib.AsrkError(what + ": s must be an int32 [B, T] device tensor (ops.rnnt_prune_ranges)")
+    return s.contiguous()
+
+
+class RNNTSimpleLossFn(Function):
+    """RNNTSimpleLossFn.apply(am [B,T,V], lm [B,U+1,V], targets [B,L], enc_len [B], txt_len [B], blank=0) ->
+    (nll [B], occ [B,T,U+1]): the transducer loss of the additive joiner am[b,t,v] + lm[b,u,v], whose [B,T,U+1,V] sum is
+    never stored (asrk_rnnt_simple_rows_f32, the dense lattice, asrk_rnnt_simple_occ_f32), and, detached, the occupation
+    occ = eb + el of the arcs leaving every cell, which ops.rnnt_prune_ranges turns into the band.  The backward
+    (asrk_rnnt_simple_grad_f32) gives dam and dlm without atomics."""
+
+    @staticmethod
+    def forward(ctx, am, lm, targets, enc_len, txt_len, blank=0):
+        _require_gpu(am)
+        am, lm = _f32c(am), _f32c(lm)
+        if am.dim() != 3 or lm.dim() != 3 or am.shape[0] != lm.shape[0] or am.shape[2] != lm.shape[2]:
+            raise _lib.AsrkError("RNNTSimpleLossFn: am must be [B, T, V] and lm [B, U + 1, V]")
+        B, T, V = am.shape
+        U1 = lm.shape[1]
+        dev = am.device
+        txt, el, tl = _rnnt_lengths("RNNTSimpleLossFn", targets, enc_len, txt_len, B, U1, dev)
+        L = _L()
+        lse = torch.empty((B, T, U1), dtype=torch.float32, device=dev)
+        lpb, lpl, alpha, beta = (torch.empty_like(lse) for _ in range(4))
+        c, eb, el_ = (torch.empty_like(lse) for _ in range(3))
+        nll = torch.empty((B,), dtype=torch.float32, device=dev)
+        _lib.check(L.asrk_rnnt_simple_rows_f32(_p(am), V, _p(lm), V, _p(txt), txt.shape[1], _p(el), _p(tl), B, T, U1, V,
+                                               blank, _p(lse), _p(lpb), _p(lpl), _stream()), "rnnt_simple_rows")
+        _lib.check(L.asrk_rnnt_lattice_f32(_p(lpb), _p(lpl), _p(el), _p(tl), B, T, U1, _p(alpha), _p(beta), _p(nll),
+                                           _stream()), "rnnt_lattice")
+        _lib.check(L.asrk_rnnt_simple_occ_f32(_p(lpb), _p(lpl), _p(alpha), _p(beta), _p(nll), _p(el), _p(tl), B, T, U1,
+                                              _p(c), _p(eb), _p(el_), _stream()), "rnnt_simple_occ")
+        occ = eb + el_
+        ctx.save_for_backward(am, lm, txt, el, tl, lse, c, eb, el_)
+        ctx.blank = blank
+        ctx.mark_non_differentiable(occ)
+        return nll, occ
+
+    @staticmethod
+    def backward(ctx, gnll, _gocc):
+        am, lm, txt, el, tl, lse, c, eb, el_ = ctx.saved_tensors
+        B, T, V = am.shape
+        U1 = lm.shape[1]
+        gscale = gnll.to(torch.float32).contiguous()
+        dam, dlm = torch.empty_like(am), torch.empty_like(lm)
+        _lib.check(_L().asrk_rnnt_simple_grad_f32(_p(am), V, _p(lm), V, _p(txt), txt.shape[1], _p(el), _p(tl), B, T, U1,
+                                                  V, ctx.blank, _p(lse), _p(c), _p(eb), _p(el_), _p(gscale), _p(dam), V,
+                                                  _p(dlm), V, _stream()), "rnnt_simple_grad")
+        return dam, dlm, None, None, None, None
+
+
+@torch.no_grad()
+def rnnt_prune_ranges(occ, enc_len, txt_len, prune_range):
+    """occ [B,T,U+1] (RNNTSimpleLossFn's second result) -> s int32 [B,T], the first of the `prune_range` label positions
+    kept at every frame (asrk_rnnt_prune_ranges_f32; the rule: csrc/rnnt_prune.inc)."""
+    _require_gpu(occ)
+    occ = _f32c(occ)
+    S = int(prune_range)
+    if occ.dim() != 3 or not 1 <= S <= RNNT_PRUNE_MAX_RANGE:
+        raise _lib.AsrkError("rnnt_prune_ranges: occ must be [B, T, U + 1] and 1 <= prune_range <= %d"
+                             % RNNT_PRUNE_MAX_RANGE)
+    B, T, U1 = occ.shape
+    dev = occ.device
+    el = torch.as_tensor(enc_len).to(device=dev, dtype=torch.int64).contiguous()
+    tl = torch.as_tensor(txt_len).to(device=dev, dtype=torch.int64).contiguous()
+    if el.numel() != B or tl.numel() != B:
+        raise _lib.AsrkError("rnnt_prune_ranges: one enc_len and one txt_len per utterance")
+    s = torch.empty((B, T), dtype=torch.int32, device=dev)
+    _lib.check(_L().asrk_rnnt_prune_ranges_f32(_p(occ), _p(el), _p(tl), B, T, U1, S, _p(s), _stream()),
+               "rnnt_prune_ranges")
+    return s
+
+
+class RNNTJointBandFn(Function):
+    """RNNTJointBandFn.apply(E [B,T,J], P [B,U+1,J], s int32 [B,T], S) -> H [B,T,S,J] = tanh(E[b,t] + P[b, min(s[b,t] + k,
+    U)]) (asrk_rnnt_joint_band_f32); the backward sums dH * (1 - H^2) over k into dE and over the (t, k) that read row u
+    into dP (asrk_rnnt_joint_band_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, E, P, s, S):
+        _require_gpu(E)
+        E, P = _f32c(E), _f32c(P)
+        S = int(S)
+        if E.dim() != 3 or P.dim() != 3 or E.shape[0] != P.shape[0] or E.shape[2] != P.shape[2]:
+            raise _lib.AsrkError("RNNTJointBandFn: E must be [B, T, J] and P [B, U + 1, J]")
+        if not 1 <= S <= RNNT_PRUNE_MAX_RANGE:
+            raise _lib.AsrkError("RNNTJointBandFn: 1 <= S <= %d" % RNNT_PRUNE_MAX_RANGE)
+        B, T, J = E.shape
+        U1 = P.shape[1]
+        s = _band_starts("RNNTJointBandFn", s, B, T, E.device)
+        H = torch.empty((B, T, S, J), dtype=torch.float32, device=E.device)
+        _lib.check(_L().asrk_rnnt_joint_band_f32(_p(E), J, _p(P), J, _p(s), B, T, S, U1, J, _p(H), J, _stream()),
+                   "rnnt_joint_band")
+        ctx.save_for_backward(H, s)
+        ctx.U1 = U1
+        return H
+
+    @staticmethod
+    def backward(ctx, dH):
+        H, s = ctx.saved_tensors
+        B, T, S, J = H.shape
+        U1 = ctx.U1
+        dH = _f32c(dH)
+        dE = torch.empty((B, T, J), dtype=torch.float32, device=H.device)
+        dP = torch.empty((B, U1, J), dtype=torch.float32, device=H.device)
+        _lib.check(_L().asrk_rnnt_joint_band_bwd_f32(_p(H), J, _p(dH), J, _p(s), B, T, S, U1, J, _p(dE), J, _p(dP), J,
+                                                     _stream()), "rnnt_joint_band_bwd")
+        return dE, dP, None, None
+
+
+class RNNTBandLossFn(Function):
+    """RNNTBandLossFn.apply(logits [B,T,S,V], targets [B,L], enc_len, txt_len, s int32 [B,T], U1, blank, reduction,
+    consume_logits): the dense transducer loss with lpb = lpl = -inf at every cell outside the band u in [s[b,t], s[b,t]
+    + S).  Row pass on the band (asrk_rnnt_rows_band_f32), its lpb / lpl scattered into -inf-filled [B,T,U1] arrays, the
+    dense lattice, and the gradient pass on the band (asrk_rnnt_grad_band_f32), in place with consume_logits.  An
+    utterance whose band holds no path has nll = +inf and an all-zero gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, enc_len, txt_len, s, U1, blank=0, reduction="mean", consume_logits=False):
+        _require_gpu(logits)
+        if logits.dim() != 4:
+            raise _lib.AsrkError("RNNTBandLoss: logits must be [B, T, S, V]")
+        x = _f32c(logits)
+        B, T, S, V = x.shape
+        U1 = int(U1)
+        dev = x.device
+        txt, el, tl = _rnnt_lengths("RNNTBandLoss", targets, enc_len, txt_len, B, U1, dev)
+        s = _band_starts("RNNTBandLoss", s, B, T, dev)
+        L = _L()
+        lse = torch.empty((B, T, S), dtype=torch.float32, device=dev)
+        lpb_b, lpl_b = torch.empty_like(lse), torch.empty_like(lse)
+        lpb = torch.empty((B, T, U1), dtype=torch.float32, device=dev)
+        lpl, alpha, beta = torch.empty_like(lpb), torch.empty_like(lpb), torch.empty_like(lpb)
+        nll = torch.empty((B,), dtype=torch.float32, device=dev)
+        _lib.check(L.asrk_rnnt_rows_band_f32(_p(x), V, _p(txt), txt.shape[1], _p(el), _p(tl), _p(s), B, T, S, U1, V, blank,
+                                             _p(lse), _p(lpb_b), _p(lpl_b), _stream()), "rnnt_rows_band")
+        _lib.check(L.asrk_rnnt_band_scatter_f32(_p(lpb_b), _p(lpl_b), _p(s), _p(el), _p(tl), B, T, S, U1, _p(lpb), _p(lpl),
+                                                _stream()), "rnnt_band_scatter")
+        _lib.check(L.asrk_rnnt_lattice_f32(_p(lpb), _p(lpl), _p(el), _p(tl), B, T, U1, _p(alpha), _p(beta), _p(nll),
+                                           _stream()), "rnnt_lattice")
+        ctx.save_for_backward(x, txt, el, tl, s, lse, lpb, lpl, alpha, beta, nll)
+        ctx.meta = (U1, blank, reduction, bool(consume_logits))
+        if reduction == "mean":
+            return nll.mean()
+        if reduction == "sum":
+            return nll.sum()
+        return nll
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, txt, el, tl, s, lse, lpb, lpl, alpha, beta, nll = ctx.saved_tensors
+        U1, blank, reduction, consume = ctx.meta
+        B, T, S, V = x.shape
+        g = gout.to(torch.float32)
+        if reduction == "mean":
+            gscale = (g / B).expand(B)
+        elif reduction == "sum":
+            gscale = g.expand(B)
+        else:
+            gscale = g
+        gscale = gscale.contiguous()
+        dz = x if consume else torch.empty_like(x)
+        _lib.check(_L().asrk_rnnt_grad_band_f32(_p(x), V, _p(txt), txt.shape[1], _p(el), _p(tl), _p(s), B, T, S, U1, V,
+                                                blank, _p(lse), _p(lpb), _p(lpl), _p(alpha), _p(beta), _p(nll),
+                                                _p(gscale), _p(dz), V, _stream()), "rnnt_grad_band")
+        return (dz,) + (None,) * 8
+
+
+class RNNTBandLoss(torch.nn.Module):
+    """Transducer loss on band logits [B, T, S, V] (RNNTJointBandFn -> lin_out): forward(logits, targets, enc_len,
+    txt_len, s, consume_logits=False), `s` from ops.rnnt_prune_ranges; U + 1 is targets.shape[1] + 1 unless U1 is
+    given.  Reductions as ops.RNNTLoss."""
+
+    def __init__(self, blank=0, reduction="mean"):
+        super().__init__()
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError("RNNTBandLoss: unknown reduction %r" % (reduction,))
+        self.blank = blank
+        self.reduction = reduction
+
+    def forward(self, logits, targets, enc_len, txt_len, s, consume_logits=False, U1=None):
+        U1 = int(torch.as_tensor(targets).shape[1]) + 1 if U1 is None else int(U1)
+        return RNNTBandLossFn.apply(logits, targets, enc_len, txt_len, s, U1, self.blank, self.reduction, consume_logits)
+
+
 # --------------------------------------------------------------------------- cross entropy
 def _check_label_smoothing(eps):
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:

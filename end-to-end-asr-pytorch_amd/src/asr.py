@@ -10,7 +10,7 @@ from .. import ops
 from .. import decoder_ops as dops
 from .. import speller_ops as sops
 from .util import init_weights, init_gate
-from .transducer import TransducerHead, transducer_enabled
+from .transducer import TransducerHead, transducer_enabled, take_prune_block
 from .module import (VGGExtractor, CNNExtractor, RNNLayer, RNNParams, ScaleDotAttention,
                      LocationAwareAttention)
 
@@ -45,13 +45,16 @@ class ASR(nn.Module):
         # RNN-transducer head (the `model: transducer:` block; absent or enable: false = no new parameter, no new key)
         self.enable_rnnt = transducer_enabled(transducer)
         self.rnnt_weight = 0.0
+        self.rnnt_prune = None
         if self.enable_rnnt:
-            unknown = sorted(set(transducer) - {'enable', 'weight', 'joint_dim', 'pred'}, key=str)
+            unknown = sorted(set(transducer) - {'enable', 'weight', 'joint_dim', 'pred', 'prune'}, key=str)
             if unknown:
                 raise ValueError('model.transducer: unknown key(s) {}'.format(unknown))
             self.rnnt_weight = float(transducer.get('weight', 0.3))
+            # pruned training (the `prune:` sub-block; absent or enable: false = no new parameter, no new key)
+            self.rnnt_prune = take_prune_block(transducer.get('prune'))
             self.transducer = TransducerHead(vocab_size, self.encoder.out_dim, dict(transducer.get('pred') or {}),
-                                             int(transducer.get('joint_dim', 512)))
+                                             int(transducer.get('joint_dim', 512)), prune=self.rnnt_prune)
 
         if init_adadelta:
             self.apply(init_weights)
@@ -93,6 +96,16 @@ class ASR(nn.Module):
             ASR.forward(encoded=...)), for ops.RNNTLoss(consume_logits=True); txt [B,L] padded labels, txt_len [B] '''
         self._need_transducer('transducer_logits')
         return self.transducer(encode_feature, encode_len, txt, txt_len)
+
+    def transducer_loss_pruned(self, encode_feature, encode_len, txt, txt_len):
+        ''' the pruned transducer training loss on the encoder's output (`model: transducer: prune:`) ->
+            (pruned_nll + simple_weight * simple_nll, pruned_nll, simple_nll), means over the utterances; the head's
+            weight is the caller's (TransducerHead.forward_pruned) '''
+        self._need_transducer('transducer_loss_pruned')
+        if self.rnnt_prune is None:
+            raise RuntimeError('ASR.transducer_loss_pruned needs the `model: transducer: prune:` block')
+        pruned, simple = self.transducer.forward_pruned(encode_feature, encode_len, txt, txt_len)
+        return pruned + self.rnnt_prune['simple_weight'] * simple, pruned, simple
 
     @torch.no_grad()
     def transducer_greedy(self, audio_feature, feature_len, max_symbols=3, max_len_ratio=0.5):

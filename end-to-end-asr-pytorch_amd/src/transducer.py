@@ -2,6 +2,9 @@
 joint network tanh(lin_enc(enc)[b,t] + lin_pred(pred)[b,u]) -> lin_out -> [B, T', U+1, V] logits for ops.RNNTLoss, and
 batched greedy decoding with device-resident bookkeeping (csrc/rnnt.hip) and an alignment-length-synchronous beam search
 with merged alignments and n-gram LM fusion (csrc/rnnt_beam.hip).  Blank = <sos> = 0.
+With the `prune:` sub-block the training loss is the pruned one (Kuang et al. 2022; csrc/rnnt_prune.hip): an additive
+joiner lin_am(enc)[b,t] + lin_lm(pred)[b,u] on the whole lattice picks `range` label positions per frame, and the joint
+network and the loss run on that band only.
 """
 import torch
 import torch.nn as nn
@@ -30,6 +33,46 @@ def check_exclusive(config):
         raise ValueError('config blocks `model: transducer:` and `mwer:` cannot be combined')
     if bool((config.get('emb') or {}).get('enable', False)):
         raise ValueError('config blocks `model: transducer:` and `emb:` cannot be combined')
+
+
+PRUNE_KEYS = ('enable', 'range', 'simple_weight')
+PRUNE_MAX_RANGE = 32
+
+
+def take_prune_block(block):
+    ''' validates the `model: transducer: prune:` sub-block and returns {range, simple_weight} when it is enabled, else
+        None.  range (whole number in 2..32, default 5) is the number of label positions kept per frame, simple_weight
+        (>= 0, default 0.5) the weight of the simple joiner's loss beside the pruned one. '''
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError('model.transducer.prune: expected a mapping, got %r' % (block,))
+    unknown = sorted(set(block) - set(PRUNE_KEYS), key=str)
+    if unknown:
+        raise ValueError('model.transducer.prune: unknown key(s) {}'.format(unknown))
+    opts = {}
+    for key, default in (('range', 5), ('simple_weight', 0.5)):
+        v = block.get(key, default)
+        ok = not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float('inf')
+        if not ok or (key == 'range' and v != int(v)):
+            raise ValueError('model.transducer.prune: {} must be a {}, got {!r}'.format(
+                key, 'whole number' if key == 'range' else 'finite number', v))
+        opts[key] = int(v) if key == 'range' else float(v)
+    if not 2 <= opts['range'] <= PRUNE_MAX_RANGE:
+        raise ValueError('model.transducer.prune: range must be in 2..{}, got {}'.format(PRUNE_MAX_RANGE, opts['range']))
+    if not opts['simple_weight'] >= 0:
+        raise ValueError('model.transducer.prune: simple_weight must be >= 0, got {}'.format(opts['simple_weight']))
+    if not isinstance(block.get('enable', True), (bool, int)):
+        raise ValueError('model.transducer.prune: enable must be true or false, got {!r}'.format(block.get('enable')))
+    return opts if block.get('enable', True) else None
+
+
+def infeasible_utterances(enc_len, txt_len, prune_range):
+    ''' indices b with (T_b - 1)(S - 1) < max(0, U_b + 1 - S): a band of S positions that moves at most S - 1 per frame
+        cannot cover such a transcript (host lengths) '''
+    S = int(prune_range)
+    return [b for b, (t, u) in enumerate(zip(enc_len, txt_len))
+            if (max(int(t), 1) - 1) * (S - 1) < max(0, int(u) + 1 - S)]
 
 
 BEAM_KEYS = ('beam_size', 'nbest', 'lm_weight')
@@ -83,9 +126,11 @@ def uses_beam(opts):
 
 class TransducerHead(nn.Module):
     ''' vocab_size: V (index 0 is blank and <sos>); enc_dim: encoder output width;
-        pred = {module: LSTM|GRU, dim, layer, emb_dim, dropout}; joint_dim: J '''
+        pred = {module: LSTM|GRU, dim, layer, emb_dim, dropout}; joint_dim: J;
+        prune = {range, simple_weight} (take_prune_block's result) or None: with it the head owns the simple joiner's
+        two projections lin_am and lin_lm and forward_pruned is its training forward '''
 
-    def __init__(self, vocab_size, enc_dim, pred, joint_dim):
+    def __init__(self, vocab_size, enc_dim, pred, joint_dim, prune=None):
         super().__init__()
         unknown = set(pred) - set(PRED_KEYS)
         if unknown:
@@ -107,10 +152,17 @@ class TransducerHead(nn.Module):
         self.lin_enc = nn.Linear(enc_dim, self.joint_dim)
         self.lin_pred = nn.Linear(self.dim, self.joint_dim)
         self.lin_out = nn.Linear(self.joint_dim, vocab_size)
+        self.prune = dict(prune) if prune else None
+        if self.prune:
+            self.lin_am = nn.Linear(enc_dim, vocab_size)
+            self.lin_lm = nn.Linear(self.dim, vocab_size)
 
     def create_msg(self):
-        return '           | Transducer head enabled ( {} x{} dim {}, joint dim {}).'.format(
+        msg = '           | Transducer head enabled ( {} x{} dim {}, joint dim {}).'.format(
             self.rnn_type, self.layer, self.dim, self.joint_dim)
+        if self.prune:
+            msg += ' Pruned loss ( range {}, simple weight {}).'.format(self.prune['range'], self.prune['simple_weight'])
+        return msg
 
     def _predict(self, txt):
         ''' txt [B,U] -> prediction-network output [B,U+1,dim] on <sos> + txt, from a zero state (as
@@ -137,6 +189,36 @@ class TransducerHead(nn.Module):
         P = ops.linear(self._predict(txt), self.lin_pred.weight, self.lin_pred.bias)
         H = ops.RNNTJointFn.apply(E, P)
         return ops.linear(H, self.lin_out.weight, self.lin_out.bias)
+
+    def forward_pruned(self, encode_feature, encode_len, txt, txt_len):
+        ''' the pruned training forward -> (pruned nll, simple nll), both means over the B utterances.
+            1. the simple joiner lin_am(enc)[b,t] + lin_lm(pred)[b,u] on the whole lattice (ops.RNNTSimpleLossFn: no
+               [B,T',U+1,V] tensor) gives its loss and the occupation of every cell;
+            2. ops.rnnt_prune_ranges picks the first of the S = prune.range label positions kept at every frame;
+            3. the joint network and lin_out run on the band, [B,T',S,V] logits, and ops.RNNTBandLoss is the transducer
+               loss with everything outside the band impossible; its backward writes over the logits.
+            An utterance with (T_b - 1)(S - 1) < U_b + 1 - S has no path (nll = +inf, zero gradient): with lengths on
+            the host that is a ValueError here; device lengths are not read back. '''
+        if not self.prune:
+            raise RuntimeError('TransducerHead.forward_pruned needs the `model: transducer: prune:` block')
+        S = self.prune['range']
+        if all(torch.is_tensor(x) and x.device.type == 'cpu' for x in (encode_len, txt_len)):
+            bad = infeasible_utterances(encode_len.tolist(), txt_len.tolist(), S)
+            if bad:
+                raise ValueError('transducer.prune: range {} cannot cover utterance(s) {} (encoder lengths {}, transcript '
+                                 'lengths {}): (T - 1)(range - 1) >= U + 1 - range is needed'.format(
+                                     S, bad, [int(encode_len[b]) for b in bad], [int(txt_len[b]) for b in bad]))
+        pred = self._predict(txt)
+        am = ops.linear(encode_feature, self.lin_am.weight, self.lin_am.bias)
+        lm = ops.linear(pred, self.lin_lm.weight, self.lin_lm.bias)
+        simple_nll, occ = ops.RNNTSimpleLossFn.apply(am, lm, txt, encode_len, txt_len, self.blank)
+        s = ops.rnnt_prune_ranges(occ, encode_len, txt_len, S)
+        E = ops.linear(encode_feature, self.lin_enc.weight, self.lin_enc.bias)
+        P = ops.linear(pred, self.lin_pred.weight, self.lin_pred.bias)
+        H = ops.RNNTJointBandFn.apply(E, P, s, S)
+        logits = ops.linear(H, self.lin_out.weight, self.lin_out.bias)
+        pruned_nll = ops.RNNTBandLossFn.apply(logits, txt, encode_len, txt_len, s, P.shape[1], self.blank, 'mean', True)
+        return pruned_nll, simple_nll.mean()
 
     @torch.no_grad()
     def greedy(self, encode_feature, encode_len, max_symbols, max_len):

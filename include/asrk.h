@@ -1275,6 +1275,73 @@ int asrk_rnnt_greedy_step_f32(const float *logits, int64_t ld, const int64_t *en
                               int64_t *tokens, int64_t tok_stride, int64_t *last_tok, int32_t *emit, int32_t *done,
                               void *stream);
 
+/* ---- pruned transducer training (csrc/rnnt_prune.hip, csrc/rnnt_prune.inc; TransducerHead.forward_pruned) ---------------
+ * Kuang et al. 2022: an additive joiner am[b,t,v] + lm[b,u,v] on the whole lattice tells which S consecutive label
+ * positions per frame carry the mass; the joint network and the loss then run on that band, [B,T,S,..] arrays whose cell
+ * (b,t,k) stands for u = s[b,t] + k (s int32 [B,T], clamped to [0, U1-1] by every kernel).  Lengths, txt and the lattice
+ * conventions are those of the section above; 1 <= S <= 32.
+ *
+ * Simple-joiner row pass: am [B,T,V] row stride lda, lm [B,U1,V] row stride ldl.  Per cell inside the lattice
+ *   lse = logsumexp_v(am[b,t,v] + lm[b,u,v]) (summed directly, one pass, the arithmetic of asrk_rnnt_rows_f32),
+ *   lpb = (am[t,blank] + lm[u,blank]) - lse,  lpl = (am[t,y] + lm[u,y]) - lse with y = txt[b,u], 0 at u = U_b.
+ * A workgroup owns 16 x 16 cells and streams V through LDS 64 columns at a time.  Cells outside the lattice get three
+ * zeros; rows t >= T_b of am and u > U_b of lm are never read.  asrk_rnnt_lattice_f32 runs on lpb / lpl unchanged.
+ * Call site: ops.RNNTSimpleLossFn.forward. */
+int asrk_rnnt_simple_rows_f32(const float *am, int64_t lda, const float *lm, int64_t ldl, const int64_t *txt,
+                              int64_t txt_stride, const int64_t *enc_len, const int64_t *txt_len, int B, int T, int U1,
+                              int V, int blank, float *lse, float *lpb, float *lpl, void *stream);
+/* Occupation, [B,T,U1] each, zeros outside the lattice: c = exp(alpha + beta - lnP), eb = exp(alpha + lpb + beta(t+1,u)
+ * - lnP), el = exp(alpha + lpl + beta(t,u+1) - lnP), with beta(T_b,U_b) := 0 and -inf elsewhere outside the lattice
+ * (asrk_rnnt_grad_f32's conventions).  Call site: ops.RNNTSimpleLossFn.forward. */
+int asrk_rnnt_simple_occ_f32(const float *lpb, const float *lpl, const float *alpha, const float *beta, const float *nll,
+                             const int64_t *enc_len, const int64_t *txt_len, int B, int T, int U1, float *c, float *eb,
+                             float *el, void *stream);
+/* Gradient of sum_b gscale[b] nll_b of the simple joiner, two launches:
+ *   dam[b,t,v] = gscale[b] (sum_u c(t,u) exp(am[t,v] + lm[u,v] - lse(t,u)) - [v == blank] sum_u eb(t,u)
+ *                           - sum_u [v == y_{u+1}] el(t,u)),   dlm[b,u,v] the same summed over t.
+ * A thread owns its output elements and adds the terms in ascending u (t): no atomics, bit-reproducible.  Padded rows
+ * (t >= T_b of dam, u > U_b of dlm) are written as exact zeros and not read.  Call site: ops.RNNTSimpleLossFn.backward. */
+int asrk_rnnt_simple_grad_f32(const float *am, int64_t lda, const float *lm, int64_t ldl, const int64_t *txt,
+                              int64_t txt_stride, const int64_t *enc_len, const int64_t *txt_len, int B, int T, int U1,
+                              int V, int blank, const float *lse, const float *c, const float *eb, const float *el,
+                              const float *gscale, float *dam, int64_t lddam, float *dlm, int64_t lddlm, void *stream);
+/* Pruning bounds s int32 [B,T] from occ [B,T,U1] (= eb + el), one wave per utterance.  With E_b = max(0, U_b + 1 - S):
+ *   raw(t) = argmax_{0 <= s <= E_b} sum_{u=s}^{min(s+S-1, U_b)} occ(t,u), the lowest s among equal sums;
+ *   s'(0) = 0, s'(t) = clamp(raw(t), s'(t-1), s'(t-1) + S - 1);  s(t) = max(s'(t), E_b - (T_b-1-t)(S-1)) for t < T_b,
+ *   s(t) = s(T_b-1) for padded frames.  s is non-decreasing, moves at most S-1 per frame, ends at E_b and starts at 0
+ * exactly when (T_b-1)(S-1) >= E_b; otherwise the utterance has no path inside its band.
+ * Call site: ops.rnnt_prune_ranges. */
+int asrk_rnnt_prune_ranges_f32(const float *occ, const int64_t *enc_len, const int64_t *txt_len, int B, int T, int U1,
+                               int S, int32_t *s, void *stream);
+/* Band joint: H[b,t,k,:] = tanh(E[b,t,:] + P[b, min(s[b,t]+k, U1-1), :]); H [B,T,S,J] row stride ldh.  16-byte accesses
+ * under the rule of asrk_rnnt_joint_f32.  Call site: ops.RNNTJointBandFn.forward. */
+int asrk_rnnt_joint_band_f32(const float *E, int64_t lde, const float *P, int64_t ldp, const int32_t *s, int B, int T,
+                             int S, int U1, int J, float *H, int64_t ldh, void *stream);
+/* dE[b,t,:] = sum_k dH (1 - H^2) in ascending k; dP[b,u,:] = the sum over the (t,k) with min(s[b,t]+k, U1-1) == u, in
+ * ascending t, then k.  One thread per output element, no atomics.  Call site: ops.RNNTJointBandFn.backward. */
+int asrk_rnnt_joint_band_bwd_f32(const float *H, int64_t ldh, const float *dH, int64_t lddh, const int32_t *s, int B,
+                                 int T, int S, int U1, int J, float *dE, int64_t ldde, float *dP, int64_t lddp,
+                                 void *stream);
+/* Row pass of the band loss on logits z [B*T*S, V]: asrk_rnnt_rows_f32 with cell (t,k) standing for u = s[b,t] + k
+ * (inside the lattice iff t < T_b and u <= U_b; label txt[b,u]); lse, lpb, lpl [B,T,S], zeros outside, rows outside
+ * never read.  The same one-pass log-sum-exp and the same case split at V = 2048.  Call site: ops.RNNTBandLossFn. */
+int asrk_rnnt_rows_band_f32(const float *z, int64_t ldz, const int64_t *txt, int64_t txt_stride, const int64_t *enc_len,
+                            const int64_t *txt_len, const int32_t *s, int B, int T, int S, int U1, int V, int blank,
+                            float *lse, float *lpb, float *lpl, void *stream);
+/* Band lpb / lpl [B,T,S] -> dense [B,T,U1] arrays holding -inf at every cell outside the band (or the lattice): the
+ * band loss is the dense loss on these, so asrk_rnnt_lattice_f32 computes alpha, beta and nll (+inf when the band
+ * holds no path).  Call site: ops.RNNTBandLossFn.forward. */
+int asrk_rnnt_band_scatter_f32(const float *lpb_band, const float *lpl_band, const int32_t *s, const int64_t *enc_len,
+                               const int64_t *txt_len, int B, int T, int S, int U1, float *lpb, float *lpl,
+                               void *stream);
+/* Gradient pass of the band loss: asrk_rnnt_grad_f32 per band cell; lse [B,T,S] from the row pass, lpb, lpl, alpha, beta
+ * the dense [B,T,U1] arrays.  Cells outside the lattice, and every cell of an utterance whose nll is +inf, get exact
+ * zeros written and are not read.  dz == z (then lddz == ldz) is allowed.  Call site: ops.RNNTBandLossFn.backward. */
+int asrk_rnnt_grad_band_f32(const float *z, int64_t ldz, const int64_t *txt, int64_t txt_stride, const int64_t *enc_len,
+                            const int64_t *txt_len, const int32_t *s, int B, int T, int S, int U1, int V, int blank,
+                            const float *lse, const float *lpb, const float *lpl, const float *alpha, const float *beta,
+                            const float *nll, const float *gscale, float *dz, int64_t lddz, void *stream);
+
 /* ---- transducer beam search (csrc/rnnt_beam.hip, csrc/rnnt_beam.inc; TransducerHead.beam_search) -----------------------
  * Alignment-length-synchronous search, B utterances in lock-step with W <= 32 slots each; row r = b*W + w of every
  * [B*W, ...] array.  The beam state is double buffered: arrays [2, B, ...], buffer `cur` is read and the other written.
