@@ -258,6 +258,11 @@ SIGNATURES = {
     "asrk_rnnt_band_scatter_f32": (c_int, [c_vp] * 5 + [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "asrk_rnnt_grad_band_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
                                         c_int] + [c_vp] * 8 + [c_i64, c_vp]),
+    "asrk_rnnt_ctx_fwd_f32": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
+    "asrk_rnnt_ctx_bwd_ws_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "asrk_rnnt_ctx_bwd_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "asrk_rnnt_ctx_step_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp,
+                                       c_i64, c_vp]),
 }
 
 _lib = None

@@ -2024,6 +2024,104 @@ class RNNTBandLoss(torch.nn.Module):
         return RNNTBandLossFn.apply(logits, targets, enc_len, txt_len, s, U1, self.blank, self.reduction, consume_logits)
 
 
+# --------------------------------------------------------------------------- stateless prediction network (csrc/rnnt_ctx.hip)
+RNNT_CTX_MAX = 8            # CTX_MAX_C of csrc/rnnt_ctx.hip
+
+
+def _ctx_rows(what, t, D):
+    """t [B, U1, D] f32 as rows of D floats with one row stride: (tensor, ld); a copy unless t is such a view already"""
+    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != D:
+        raise _lib.AsrkError(what + ": expected a float32 [B, U1, %d] tensor" % D)
+    if t.is_contiguous():
+        return t, D
+    ld = t.stride(1)
+    if t.stride(2) == 1 and ld >= D and t.stride(0) == t.shape[1] * ld:
+        return t, ld
+    return t.contiguous(), D
+
+
+def _ctx_weight(what, w, D):
+    if w.dim() != 3 or w.shape[0] != D or w.shape[1] != 1 or not 1 <= w.shape[2] <= RNNT_CTX_MAX:
+        raise _lib.AsrkError(what + ": w must be [D, 1, C] with 1 <= C <= %d" % RNNT_CTX_MAX)
+    return _f32c(w)
+
+
+@torch.no_grad()
+def rnnt_ctx_fwd(X, w, out=None):
+    """Y[b,u,d] = relu(sum_j w[d,0,j] X[b, u-(C-1)+j, d]) (asrk_rnnt_ctx_fwd_f32): X [B,U1,D] and `out` may be row-strided
+    views (last stride 1, one stride between consecutive rows of [B*U1]); w [D,1,C]"""
+    _require_gpu(X)
+    if X.dim() != 3:
+        raise _lib.AsrkError("rnnt_ctx_fwd: X must be [B, U1, D]")
+    B, U1, D = X.shape
+    w = _ctx_weight("rnnt_ctx_fwd", w, D)
+    x, ldx = _ctx_rows("rnnt_ctx_fwd", X if X.dtype == torch.float32 else X.float(), D)
+    if out is None:
+        out = torch.empty((B, U1, D), dtype=torch.float32, device=X.device)
+    y, ldy = _ctx_rows("rnnt_ctx_fwd", out, D)
+    if y is not out:
+        raise _lib.AsrkError("rnnt_ctx_fwd: out must be a row-strided [B, U1, D] view")
+    _lib.check(_L().asrk_rnnt_ctx_fwd_f32(_p(x), ldx, _p(w), B, U1, D, w.shape[2], _p(y), ldy, _stream()), "rnnt_ctx_fwd")
+    return out
+
+
+class RNNTContextFn(Function):
+    """RNNTContextFn.apply(X [B,U1,D], w [D,1,C]) -> Y [B,U1,D]: the stateless prediction network on the embedded labels,
+    a causal depthwise convolution over the last C positions and a ReLU (asrk_rnnt_ctx_fwd_f32).  The backward
+    (asrk_rnnt_ctx_bwd_f32) takes the derivative at a pre-activation of exactly 0 as 0 and reduces dw in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, X, w):
+        _require_gpu(X)
+        X, w = _f32c(X), _f32c(w)
+        Y = rnnt_ctx_fwd(X, w)
+        ctx.save_for_backward(X, w, Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, w, Y = ctx.saved_tensors
+        B, U1, D = X.shape
+        C = w.shape[2]
+        dY = _f32c(dY)
+        dX, dw = torch.empty_like(X), torch.empty_like(w)
+        if B * U1 == 0:
+            return dX, dw.zero_()
+        L = _L()
+        nbytes = int(L.asrk_rnnt_ctx_bwd_ws_bytes(B, U1, D, C))
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=X.device)
+        _lib.check(L.asrk_rnnt_ctx_bwd_f32(_p(X), _p(w), _p(Y), _p(dY), B, U1, D, C, _p(dX), _p(dw), _p(ws), nbytes,
+                                           _stream()), "rnnt_ctx_bwd")
+        return dX, dw
+
+
+@torch.no_grad()
+def rnnt_ctx_step(tokens, n_tok, emb_weight, w, out=None):
+    """the decode form (asrk_rnnt_ctx_step_f32): row r of tokens [R, Lc] (int64: the greedy state's; int32: one buffer of
+    the beam state's [B, W, Lc], taken as [B*W, Lc]) with n_tok[r] labels -> [R, D], the prediction-network output after
+    <sos> and those labels, gathered straight from the embedding matrix emb_weight [V, D]; w [D,1,C]"""
+    _require_gpu(emb_weight)
+    if tokens.dtype not in (torch.int32, torch.int64) or tokens.dim() < 2 or not tokens.is_contiguous():
+        raise _lib.AsrkError("rnnt_ctx_step: tokens must be a contiguous int32 / int64 [..., Lc] tensor")
+    Lc = tokens.shape[-1]
+    R = tokens.numel() // Lc if Lc else 0
+    if n_tok.dtype != torch.int32 or n_tok.numel() != R or not n_tok.is_contiguous():
+        raise _lib.AsrkError("rnnt_ctx_step: n_tok must be contiguous int32, one per row of tokens")
+    if emb_weight.dim() != 2:
+        raise _lib.AsrkError("rnnt_ctx_step: emb_weight must be [V, D]")
+    emb = _f32c(emb_weight)
+    V, D = emb.shape
+    w = _ctx_weight("rnnt_ctx_step", w, D)
+    if out is None:
+        out = torch.empty((R, D), dtype=torch.float32, device=emb.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (R, D) or (D > 1 and out.stride(1) != 1):
+        raise _lib.AsrkError("rnnt_ctx_step: out must be a float32 [R, D] tensor with unit last stride")
+    ldy = out.stride(0) if R > 1 else max(out.stride(0), D)
+    _lib.check(_L().asrk_rnnt_ctx_step_f32(_p(tokens), tokens.element_size(), Lc, _p(n_tok), R, Lc, _p(emb), V, D, _p(w),
+                                           w.shape[2], _p(out), ldy, _stream()), "rnnt_ctx_step")
+    return out
+
+
 # --------------------------------------------------------------------------- cross entropy
 def _check_label_smoothing(eps):
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:

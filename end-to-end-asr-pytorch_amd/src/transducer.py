@@ -1,11 +1,15 @@
-"""RNN-transducer head (Graves 2012) on the pyramidal encoder: embedding + unidirectional LSTM/GRU prediction network,
-joint network tanh(lin_enc(enc)[b,t] + lin_pred(pred)[b,u]) -> lin_out -> [B, T', U+1, V] logits for ops.RNNTLoss, and
-batched greedy decoding with device-resident bookkeeping (csrc/rnnt.hip) and an alignment-length-synchronous beam search
-with merged alignments and n-gram LM fusion (csrc/rnnt_beam.hip).  Blank = <sos> = 0.
+"""RNN-transducer head (Graves 2012) on the pyramidal encoder: embedding + unidirectional LSTM/GRU prediction network
+(or the stateless one of Ghodsi et al. 2020: a causal depthwise convolution over the last `context` label embeddings and
+a ReLU; csrc/rnnt_ctx.hip), joint network tanh(lin_enc(enc)[b,t] + lin_pred(pred)[b,u]) -> lin_out -> [B, T', U+1, V]
+logits for ops.RNNTLoss, and batched greedy decoding with device-resident bookkeeping (csrc/rnnt.hip) and an
+alignment-length-synchronous beam search with merged alignments and n-gram LM fusion (csrc/rnnt_beam.hip).
+Blank = <sos> = 0.
 With the `prune:` sub-block the training loss is the pruned one (Kuang et al. 2022; csrc/rnnt_prune.hip): an additive
 joiner lin_am(enc)[b,t] + lin_lm(pred)[b,u] on the whole lattice picks `range` label positions per frame, and the joint
 network and the loss run on that band only.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -15,7 +19,23 @@ from .. import gru_ops
 from .module import RNNParams
 
 
-PRED_KEYS = ('module', 'dim', 'layer', 'emb_dim', 'dropout')
+PRED_KEYS = ('module', 'dim', 'layer', 'emb_dim', 'dropout', 'context')
+CONTEXT_MAX = 8             # ops.RNNT_CTX_MAX
+
+
+class ContextParams(nn.Module):
+    """Parameter container of the stateless prediction network: `weight` [dim, 1, context] with the name, shape and
+    default init of nn.Conv1d(dim, dim, context, groups=dim, bias=False), so a torch module built at the same point of
+    the random stream holds the same values.  It never runs ATen's convolution (ops.RNNTContextFn does the work)."""
+
+    def __init__(self, dim, context):
+        super().__init__()
+        self.dim, self.context = dim, context
+        self.weight = nn.Parameter(torch.empty(dim, 1, context))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))     # uniform(+-1/sqrt(context)), as nn.Conv1d
 
 
 def transducer_enabled(cfg):
@@ -126,18 +146,22 @@ def uses_beam(opts):
 
 class TransducerHead(nn.Module):
     ''' vocab_size: V (index 0 is blank and <sos>); enc_dim: encoder output width;
-        pred = {module: LSTM|GRU, dim, layer, emb_dim, dropout}; joint_dim: J;
+        pred = {module: LSTM|GRU, dim, layer, emb_dim, dropout} or {module: stateless, dim, context, dropout} (context:
+        whole number in 1..8, default 2; the head then owns emb [V, dim] and ctx.weight [dim, 1, context] and no pred.*);
+        joint_dim: J;
         prune = {range, simple_weight} (take_prune_block's result) or None: with it the head owns the simple joiner's
         two projections lin_am and lin_lm and forward_pruned is its training forward '''
 
     def __init__(self, vocab_size, enc_dim, pred, joint_dim, prune=None):
         super().__init__()
-        unknown = set(pred) - set(PRED_KEYS)
-        if unknown:
-            raise ValueError('transducer: unknown pred keys {}'.format(sorted(unknown)))
         module = str(pred.get('module', 'LSTM')).upper()
-        if module not in ('LSTM', 'GRU'):
-            raise NotImplementedError("transducer prediction network '{}' is not supported (LSTM / GRU)".format(module))
+        self.stateless = module == 'STATELESS'
+        unknown = set(pred) - set(PRED_KEYS if self.stateless else PRED_KEYS[:-1])
+        if unknown:
+            raise ValueError('transducer: unknown pred keys {}'.format(sorted(unknown, key=str)))
+        if module not in ('LSTM', 'GRU', 'STATELESS'):
+            raise NotImplementedError("transducer prediction network '{}' is not supported (LSTM / GRU / stateless)"
+                                      .format(module))
         self.vocab_size = vocab_size
         self.rnn_type = module
         self.dim = int(pred.get('dim', 512))
@@ -146,9 +170,25 @@ class TransducerHead(nn.Module):
         self.dropout = float(pred.get('dropout', 0.0))
         self.joint_dim = int(joint_dim)
         self.blank = 0
-        self.emb = nn.Embedding(vocab_size, self.emb_dim)
-        self.pred = RNNParams(module, self.emb_dim, self.dim, num_layers=self.layer, dropout=self.dropout,
-                              batch_first=True)
+        if self.stateless:
+            c = pred.get('context', 2)
+            if isinstance(c, bool) or not isinstance(c, (int, float)) or c != c or c != int(c) \
+                    or not 1 <= int(c) <= CONTEXT_MAX:
+                raise ValueError('transducer: pred.context must be a whole number in 1..{}, got {!r}'.format(
+                    CONTEXT_MAX, c))
+            if self.emb_dim != self.dim:
+                raise ValueError('transducer: the stateless prediction network is depthwise: pred.emb_dim ({}) must '
+                                 'equal pred.dim ({})'.format(self.emb_dim, self.dim))
+            if self.layer != 1:
+                raise ValueError('transducer: the stateless prediction network has one layer, got pred.layer = {}'
+                                 .format(self.layer))
+            self.context = int(c)
+            self.emb = nn.Embedding(vocab_size, self.dim)
+            self.ctx = ContextParams(self.dim, self.context)
+        else:
+            self.emb = nn.Embedding(vocab_size, self.emb_dim)
+            self.pred = RNNParams(module, self.emb_dim, self.dim, num_layers=self.layer, dropout=self.dropout,
+                                  batch_first=True)
         self.lin_enc = nn.Linear(enc_dim, self.joint_dim)
         self.lin_pred = nn.Linear(self.dim, self.joint_dim)
         self.lin_out = nn.Linear(self.joint_dim, vocab_size)
@@ -158,8 +198,12 @@ class TransducerHead(nn.Module):
             self.lin_lm = nn.Linear(self.dim, vocab_size)
 
     def create_msg(self):
-        msg = '           | Transducer head enabled ( {} x{} dim {}, joint dim {}).'.format(
-            self.rnn_type, self.layer, self.dim, self.joint_dim)
+        if self.stateless:
+            msg = '           | Transducer head enabled ( stateless predictor, context {}, dim {}, joint dim {}).'.format(
+                self.context, self.dim, self.joint_dim)
+        else:
+            msg = '           | Transducer head enabled ( {} x{} dim {}, joint dim {}).'.format(
+                self.rnn_type, self.layer, self.dim, self.joint_dim)
         if self.prune:
             msg += ' Pruned loss ( range {}, simple weight {}).'.format(self.prune['range'], self.prune['simple_weight'])
         return msg
@@ -171,6 +215,9 @@ class TransducerHead(nn.Module):
         B = txt.shape[0]
         inp = torch.cat([torch.zeros((B, 1), dtype=torch.int64, device=dev), txt.to(device=dev, dtype=torch.int64)],
                         dim=1)
+        if self.stateless:      # embedding -> dropout -> context convolution + ReLU: one pass, no recurrence
+            return ops.RNNTContextFn.apply(ops.dropout(dops.embedding(inp, self.emb.weight), self.dropout, self.training),
+                                           self.ctx.weight)
         h = ops.swap_bt(ops.dropout(dops.embedding(inp, self.emb.weight), self.dropout, self.training))
         for l in range(self.layer):
             if self.rnn_type == 'LSTM':
@@ -234,6 +281,16 @@ class TransducerHead(nn.Module):
         enc_len = torch.as_tensor(encode_len).to(device=dev, dtype=torch.int64).contiguous()
         E = ops.linear(encode_feature, self.lin_enc.weight, self.lin_enc.bias)
         st = ops.rnnt_greedy_state(B, max_len, dev)
+        if self.stateless:
+            # no state to keep: the last `context` labels of every row are in st.tokens / st.n_tok, so the P rows of the
+            # next iteration are one context step on the bookkeeping just written and lin_pred
+            P = self._ctx_rows(st.tokens, st.n_tok)
+            for _ in range(T + max_len):
+                H = ops.rnnt_joint_step(E, P, st.t_ptr)
+                logits = ops.linear(H, self.lin_out.weight, self.lin_out.bias)
+                ops.rnnt_greedy_step(logits, enc_len, T, st, max_symbols, max_len, self.blank)
+                P = self._ctx_rows(st.tokens, st.n_tok)
+            return st.tokens[:, :max_len], st.n_tok
         lstm = self.rnn_type == 'LSTM'
         n_state = self.layer * (2 if lstm else 1)
         widths = [self.dim] * n_state + [self.joint_dim]
@@ -269,6 +326,11 @@ class TransducerHead(nn.Module):
             self._select(cur, nxt, torch.add(ar, st.emit, alpha=B), widths)
             k = 1 - k
         return st.tokens[:, :max_len], st.n_tok
+
+    def _ctx_rows(self, tokens, n_tok):
+        ''' stateless head: lin_pred of the prediction-network output after <sos> and the n_tok[r] labels of row r '''
+        return ops.linear(ops.rnnt_ctx_step(tokens, n_tok.view(-1), self.emb.weight, self.ctx.weight),
+                          self.lin_pred.weight, self.lin_pred.bias)
 
     @staticmethod
     def _select(src, dst, parent, widths):
@@ -331,6 +393,10 @@ class TransducerHead(nn.Module):
         enc_len = torch.as_tensor(encode_len).to(device=dev, dtype=torch.int64).contiguous()
         E = ops.linear(encode_feature, self.lin_enc.weight, self.lin_enc.bias)
         st = ops.rnnt_beam_state(B, W, K, max_len, dev)
+        if self.stateless:
+            yield from self._beam_steps_stateless(E, enc_len, st, T, max_symbols, max_len, lm if use_lm else None,
+                                                  lm_weight)
+            return
         lstm = self.rnn_type == 'LSTM'
         n_state = self.layer * (2 if lstm else 1)
         widths = [self.dim] * n_state + [self.joint_dim]
@@ -375,6 +441,37 @@ class TransducerHead(nn.Module):
             step_cells(work, st.last_tok)
             self._select(work, kept, st.sel, widths)
             if use_lm:
+                lm(st.last_tok.view(R, 1), None, lm_state[k][0].view(torch.int32), parent=st.parent,
+                   out=lm_rows[k][1], state_out=lm_state[k][1].view(torch.int32))
+                dops.gather_rows_multi([(lm_rows[k], lm_rows[1 - k][0], V, 1, False),
+                                        (lm_state[k], lm_state[1 - k][0], 1, 1, False)], st.lm_sel)
+                k = 1 - k
+            yield i, st
+
+    def _beam_steps_stateless(self, E, enc_len, st, T, max_symbols, max_len, lm, lm_weight):
+        ''' the loop of beam_steps for the stateless head: no kept / work buffers, no gather, no select.  After the select
+            launch has written beam buffer 1 - cur, the P rows of the next iteration are one context step on that buffer's
+            tokens / n_tok and lin_pred.  The n-gram LM branch is the one of the LSTM / GRU loop: its int32 state still
+            moves by lm_sel. '''
+        dev = E.device
+        B, W, K, V = st.B, st.W, st.K, self.vocab_size
+        R = B * W
+        if lm is not None:
+            lm_rows = [torch.zeros((2, R, V), dtype=torch.float32, device=dev) for _ in range(2)]
+            lm_state = [torch.zeros((2, R, 1), dtype=torch.float32, device=dev) for _ in range(2)]
+            lm(st.last_tok.view(R, 1), None, None, out=lm_rows[0][0], state_out=lm_state[0][0].view(torch.int32))
+        table = (st.lse, st.lpb, st.val, st.lab)
+        P = self._ctx_rows(st.tokens[0], st.n_tok[0])
+        k = 0
+        for i in range(T + max_len):
+            cur = i & 1
+            H = ops.rnnt_joint_slots(E, P, st.t_ptr[cur].view(-1), W)
+            logits = ops.linear(H, self.lin_out.weight, self.lin_out.bias)
+            ops.rnnt_beam_rows(logits, W, K, lm_rows[k][0] if lm is not None else None,
+                               lm_weight if lm is not None else 0.0, st.n_live[cur], self.blank, out=table)
+            ops.rnnt_beam_select(st, enc_len, T, max_symbols, cur)
+            P = self._ctx_rows(st.tokens[1 - cur], st.n_tok[1 - cur])
+            if lm is not None:
                 lm(st.last_tok.view(R, 1), None, lm_state[k][0].view(torch.int32), parent=st.parent,
                    out=lm_rows[k][1], state_out=lm_state[k][1].view(torch.int32))
                 dops.gather_rows_multi([(lm_rows[k], lm_rows[1 - k][0], V, 1, False),

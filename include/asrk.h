@@ -1342,6 +1342,41 @@ int asrk_rnnt_grad_band_f32(const float *z, int64_t ldz, const int64_t *txt, int
                             const float *lse, const float *lpb, const float *lpl, const float *alpha, const float *beta,
                             const float *nll, const float *gscale, float *dz, int64_t lddz, void *stream);
 
+/* ---- stateless prediction network (csrc/rnnt_ctx.hip; TransducerHead with pred.module = stateless) ----------------------
+ * Ghodsi et al. 2020: the prediction network is a causal depthwise convolution over the embeddings of the last C labels
+ * and a ReLU.  X [B,U1,D] is the embedded input <sos>, y_1 .. y_U; w [D,1,C] has the layout of a depthwise Conv1d weight
+ * (tap C-1 multiplies the current label); 1 <= C <= 8.
+ *   Y[b,u,d] = relu(sum_{j=0}^{C-1} w[d,0,j] * X[b, u-(C-1)+j, d]),
+ * positions < 0 contribute zero, the sum runs over ascending j as a chain of f32 fused multiply-adds.  All values f32, no
+ * float atomics: every result is a pure function of its inputs, reproducible bit for bit.
+ * ASRK_EINVAL, before any device call: a NULL pointer with B > 0 (R > 0), B < 0 (R < 0), any other size <= 0, a row
+ * stride below the row length.  ASRK_ESHAPE: C outside 1..8, tok_bytes not 4 or 8, B*U1 > INT32_MAX.  B == 0 (R == 0):
+ * ASRK_OK without a launch.
+ *
+ * Forward: X and Y are [B*U1] rows of D floats with row strides ldx, ldy >= D.  One pass; 16-byte accesses when X and Y
+ * are 16-byte aligned and D, ldx, ldy are multiples of 4, scalar otherwise.  Call site: ops.RNNTContextFn.forward. */
+int asrk_rnnt_ctx_fwd_f32(const float *X, int64_t ldx, const float *w, int B, int U1, int D, int C, float *Y, int64_t ldy,
+                          void *stream);
+/* Backward, contiguous arrays: with dYm = dY * (Y > 0) (the derivative at a pre-activation of exactly 0 is 0)
+ *   dX[b,u,d] = sum_j w[d,0,j] * dYm[b, u+(C-1)-j, d] over the j with u+(C-1)-j < U1, ascending j;
+ *   dw[d,0,j] = sum_{b,u} dYm[b,u,d] * X[b, u-(C-1)+j, d]: partial sums over blocks of 32 consecutive rows of [B*U1] (rows
+ *   ascending) into ws, then the blocks in ascending order.
+ * ws: caller-owned device scratch, 4-byte aligned, at least asrk_rnnt_ctx_bwd_ws_bytes(B, U1, D, C) bytes, private to the
+ * call until the stream has passed it; ASRK_EWORKSPACE if NULL, misaligned or smaller.  ASRK_ESHAPE above 65535 * 32 rows.
+ * Three launches.  Call site: ops.RNNTContextFn.backward. */
+size_t asrk_rnnt_ctx_bwd_ws_bytes(int B, int U1, int D, int C);
+int asrk_rnnt_ctx_bwd_f32(const float *X, const float *w, const float *Y, const float *dY, int B, int U1, int D, int C,
+                          float *dX, float *dw, void *ws, size_t ws_bytes, void *stream);
+/* Decode step on the search state: tokens [R, ldt] (ldt >= Lc >= 1) of int32 (tok_bytes = 4, the beam state) or int64
+ * (tok_bytes = 8, the greedy state), n_tok int32 [R].  Row r at n = clamp(n_tok[r], 0, Lc) is position n of the sequence
+ * <sos>, tokens[r, 0..n-1]: tap j reads the label at n - C + j (the stored label for an index >= 0, <sos> = 0 for -1,
+ * nothing before that), gathers its row straight from emb [V, D] (no [R,C,D] intermediate) and adds in the forward's
+ * order with the forward's arithmetic, so Y[r, :] equals row n of the forward on the same labels bit for bit.  A label
+ * outside [0, V) among those the row reads makes the whole row NaN and is never used as an index (dead beam slots carry
+ * arbitrary labels).  Y [R, D] row stride ldy.  One launch.  Call site: ops.rnnt_ctx_step. */
+int asrk_rnnt_ctx_step_f32(const void *tokens, int tok_bytes, int64_t ldt, const int32_t *n_tok, int R, int Lc,
+                           const float *emb, int V, int D, const float *w, int C, float *Y, int64_t ldy, void *stream);
+
 /* ---- transducer beam search (csrc/rnnt_beam.hip, csrc/rnnt_beam.inc; TransducerHead.beam_search) -----------------------
  * Alignment-length-synchronous search, B utterances in lock-step with W <= 32 slots each; row r = b*W + w of every
  * [B*W, ...] array.  The beam state is double buffered: arrays [2, B, ...], buffer `cur` is read and the other written.
