@@ -263,6 +263,8 @@ SIGNATURES = {
     "asrk_rnnt_ctx_bwd_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "asrk_rnnt_ctx_step_f32": (c_int, [c_vp, c_int, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp,
                                        c_i64, c_vp]),
+    "asrk_rnnt_align_ws_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "asrk_rnnt_align_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_sz, c_vp]),
 }
 
 _lib = None

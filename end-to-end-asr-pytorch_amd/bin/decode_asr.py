@@ -30,10 +30,14 @@ With `beam_size: W` (> 1) or `lm_weight` (> 0) in the block the hypotheses come 
 (ASR.transducer_beam: merged alignments, n-gram LM fusion from `decode.lm_path`, which must then be an ARPA / .ngram.npz
 file); `..._output.csv` receives the best hypothesis and, with `nbest` > 1, `..._beam-<W>-<lm_weight>.csv` lists every
 hypothesis with its score.  Otherwise the greedy search runs as before.
+Two booleans of the block give token times (bin/align_rnnt.py): `align: true` turns the run into transducer forced
+alignment of both sets to their reference transcripts (no search, no LM; `..._rnnt_align.tsv` and
+`..._rnnt_align_score.tsv`), `timestamps: true` force-aligns the best hypothesis of the greedy or beam search and writes
+`..._rnnt_times.tsv` beside the usual files, which stay byte for byte what they are without the key.
 """
 import os
 
-from . import align_asr, test_asr
+from . import align_asr, align_rnnt, test_asr
 from ..parallel import gather_in_order
 from ..src.rescore import RescoreDecoder, check_decode_config
 from ..src.transducer import take_decode_block, uses_beam
@@ -69,7 +73,7 @@ class Solver(test_asr.Solver):
             # (batch size of the training config) ...
             config['decode'].setdefault('beam_size', 1)
         super().__init__(config, paras, mode)
-        if self.align:
+        if self.align or (self.transducer or {}).get('align', False):
             # ... which is replaced here by instance-wise loaders, like beam decoding.  This relies on the order
             # main.py keeps: load_data() builds the loaders from self.config AFTER __init__ has returned
             self.config['data']['corpus']['batch_size'] = 1
@@ -87,6 +91,9 @@ class Solver(test_asr.Solver):
             self.ctc_only = False
             self.enable_att = True  # (write_hyp: transducer hypotheses are never repeat-merged)
             self.transducer_lm = None
+            if self.transducer.get('align', False):
+                self.verbose(['Decode spec| Transducer forced alignment to the reference transcripts'])
+                return
             if uses_beam(self.transducer):
                 opts = self.transducer
                 if opts.get('lm_weight', 0.0) > 0:
@@ -142,11 +149,13 @@ class Solver(test_asr.Solver):
         if not getattr(self, 'transducer', None):
             return super().greedy_decode(dv_set)
         results = []
+        timestamps = self.transducer.get('timestamps', False)
         dv_set, batch_ids, _ = self._my_share(dv_set)
         for k, data in enumerate(dv_set):
             i = batch_ids[k]
             self.progress('Valid step - {}/{}'.format(i + 1, len(dv_set)))
             feat, feat_len, txt, txt_len = self.fetch_data(data)
+            first = len(results)
             if uses_beam(self.transducer):
                 opts = self.transducer
                 tokens, n_tok, score, n_hyp, _ = self.model.transducer_beam(
@@ -159,6 +168,8 @@ class Solver(test_asr.Solver):
                     if opts.get('nbest', 1) > 1:         # the scores travel with the hypotheses to write_hyp
                         hyps = [(hyp, score[j][h]) for h, hyp in enumerate(hyps)]
                     results.append((str(idx), hyps, txt[j].tolist()))
+                if timestamps:
+                    self._add_times(results, first, feat, feat_len)
                 continue
             tokens, n_tok, _ = self.model.transducer_greedy(feat, feat_len, self.transducer['max_symbols'],
                                                             self.transducer['max_len_ratio'])
@@ -166,12 +177,31 @@ class Solver(test_asr.Solver):
             for j in range(len(txt)):
                 idx = j + self.config['data']['corpus']['batch_size'] * i
                 results.append((str(idx), [tokens[j][:n_tok[j]]], txt[j].tolist()))
+            if timestamps:
+                self._add_times(results, first, feat, feat_len)
         return results
+
+    def _add_times(self, results, first, feat, feat_len):
+        ''' decode.transducer.timestamps: the rows results[first:] of the batch just searched get a fourth entry, the
+            token times of their best hypothesis (write_hyp takes it off again before the usual files are written) '''
+        best = [r[1][0] if r[1] else [] for r in results[first:]]
+        best = [h[0] if isinstance(h, tuple) else h for h in best]       # (nbest > 1: the score travels with it)
+        rows = align_rnnt.align_hypotheses(self.model, feat, feat_len, best, self.device)
+        for k, r in enumerate(rows):
+            results[first + k] = results[first + k] + (r,)
 
     def write_hyp(self, results, best_path, beam_path):
         ''' the parent's files; the n-best lists of the transducer beam search go to the beam file as well, one row per
             hypothesis with its score '''
         opts = getattr(self, 'transducer', None)
+        if opts and opts.get('timestamps', False):
+            tail = '_output.csv'
+            assert best_path.endswith(tail)
+            times_path = best_path[:-len(tail)] + '_rnnt_times.tsv'
+            align_rnnt.write_times([(r[0], r[3]) for r in results], times_path, self.tokenizer,
+                                   align_asr.frame_seconds(self))
+            self.verbose('Token times of the hypotheses are stored at {}'.format(times_path))
+            results = [r[:3] for r in results]
         if not (uses_beam(opts) and opts.get('nbest', 1) > 1):
             return super().write_hyp(results, best_path, beam_path)
         super().write_hyp([(name, [h[0] for h in hyps], truth) for name, hyps, truth in results], best_path, beam_path)
@@ -189,6 +219,8 @@ class Solver(test_asr.Solver):
     def exec(self):
         if getattr(self, 'align', False):      # (a solver assembled without __init__ decodes)
             return align_asr.run(self)
+        if (getattr(self, 'transducer', None) or {}).get('align', False):
+            return align_rnnt.run(self)
         if getattr(self, 'rescore', None):
             return self.exec_rescore()
         group = max(1, int(os.environ.get('ASRK_DECODE_BATCH', '16')))

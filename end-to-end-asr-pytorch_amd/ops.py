@@ -1698,6 +1698,113 @@ def rnnt_joint_step(E, P, t_idx):
     return H
 
 
+@torch.no_grad()
+def rnnt_rows(logits, targets, enc_len, txt_len, blank=0, out=None):
+    """The row pass alone (asrk_rnnt_rows_f32) on joint logits [B, T, U+1, V] -> (lpb, lpl) f32 [B, T, U+1]: the
+    log-probabilities of blank and of the cell's label, zeros outside every lattice.  `out`: (lpb, lpl) contiguous
+    [B, T, U+1] tensors (or slices along the batch of larger ones) to write into."""
+    _require_gpu(logits)
+    if logits.dim() != 4:
+        raise _lib.AsrkError("rnnt_rows: logits must be [B, T, U + 1, V]")
+    x = _f32c(logits)
+    B, T, U1, V = x.shape
+    dev = x.device
+    txt = torch.as_tensor(targets).to(device=dev, dtype=torch.int64)
+    if txt.dim() != 2 or txt.shape[0] != B or txt.shape[1] < U1 - 1:
+        raise _lib.AsrkError("rnnt_rows: targets must be [B, L] with L >= U")
+    txt = txt.contiguous()
+    el = torch.as_tensor(enc_len).to(device=dev, dtype=torch.int64).contiguous()
+    tl = torch.as_tensor(txt_len).to(device=dev, dtype=torch.int64).contiguous()
+    if el.numel() != B or tl.numel() != B:
+        raise _lib.AsrkError("rnnt_rows: one enc_len and one txt_len per utterance")
+    if out is None:
+        out = (torch.empty((B, T, U1), dtype=torch.float32, device=dev),
+               torch.empty((B, T, U1), dtype=torch.float32, device=dev))
+    lpb, lpl = out
+    for o in out:
+        if o.shape != (B, T, U1) or o.dtype != torch.float32 or o.device != dev or not o.is_contiguous():
+            raise _lib.AsrkError("rnnt_rows: out must be two contiguous f32 [B, T, U + 1] tensors on the logits' device")
+    lse = torch.empty((B, T, U1), dtype=torch.float32, device=dev)
+    _lib.check(_L().asrk_rnnt_rows_f32(_p(x), V, _p(txt), txt.shape[1], _p(el), _p(tl), B, T, U1, V, blank, _p(lse),
+                                       _p(lpb), _p(lpl), _stream()), "rnnt_rows")
+    return lpb, lpl
+
+
+@torch.no_grad()
+def rnnt_lattice(lpb, lpl, enc_len, txt_len):
+    """alpha, beta [B, T, U+1] and nll [B] of the transducer lattice (asrk_rnnt_lattice_f32) on the row pass's lpb /
+    lpl: what ops.rnnt_align's `lattice` argument takes."""
+    _require_gpu(lpb)
+    lpb, lpl = _f32c(lpb), _f32c(lpl)
+    if lpb.dim() != 3 or lpl.shape != lpb.shape:
+        raise _lib.AsrkError("rnnt_lattice: lpb and lpl must be [B, T, U + 1]")
+    B, T, U1 = lpb.shape
+    dev = lpb.device
+    el = torch.as_tensor(enc_len).to(device=dev, dtype=torch.int64).contiguous()
+    tl = torch.as_tensor(txt_len).to(device=dev, dtype=torch.int64).contiguous()
+    if el.numel() != B or tl.numel() != B:
+        raise _lib.AsrkError("rnnt_lattice: one enc_len and one txt_len per utterance")
+    alpha, beta = torch.empty_like(lpb), torch.empty_like(lpb)
+    nll = torch.empty((B,), dtype=torch.float32, device=dev)
+    _lib.check(_L().asrk_rnnt_lattice_f32(_p(lpb), _p(lpl), _p(el), _p(tl), B, T, U1, _p(alpha), _p(beta), _p(nll),
+                                          _stream()), "rnnt_lattice")
+    return alpha, beta, nll
+
+
+RNNTAlignment = collections.namedtuple("RNNTAlignment", ["frames", "labels_done", "tok_logp", "tok_post", "score"])
+
+
+@torch.no_grad()
+def rnnt_align(lpb, lpl, enc_len, txt_len, flags=ALIGN_BP_AUTO, lattice=None, stamps=None):
+    """Best transducer path of every utterance (asrk_rnnt_align_f32) on the row pass's lpb / lpl f32 [B, T, U+1] ->
+    RNNTAlignment of device tensors: frames int32 [B, U] (the encoder frame at which label u + 1 was emitted, -1 beyond
+    an utterance's labels), labels_done int32 [B, T] (labels emitted through frame t, -1 beyond its frames), tok_logp
+    f32 [B, U] (the label's log-probability at the emitting cell), tok_post f32 [B, U] or None (the posterior of that
+    emission, with `lattice` = (alpha, beta, nll) of ops.rnnt_lattice on the same lpb / lpl), score f32 [B] (the
+    path's log-probability; -inf, with -1 / 0 everywhere, when the transcript does not fit).  Ties emit as early as
+    possible.  `flags`: where the backpointers live (ALIGN_BP_*); the workspace of the global route is allocated
+    here.  `stamps`: optional int64 [B, 4] device tensor that receives the kernel's phase clocks."""
+    _require_gpu(lpb)
+    L = _L()
+    if lpb.dim() != 3 or lpl.shape != lpb.shape:
+        raise _lib.AsrkError("rnnt_align: lpb and lpl must be [B, T, U + 1]")
+    if lpb.dtype != torch.float32 or lpl.dtype != torch.float32:
+        raise _lib.AsrkError("rnnt_align: lpb and lpl must be float32")
+    if lpl.device != lpb.device:
+        raise _lib.AsrkError("rnnt_align: lpb and lpl must be on one device")
+    lpb, lpl = lpb.contiguous(), lpl.contiguous()
+    B, T, U1 = lpb.shape
+    if T < 1 or U1 < 1:
+        raise _lib.AsrkError("rnnt_align: T and U + 1 must be at least 1")
+    dev = lpb.device
+    el = torch.as_tensor(enc_len).to(device=dev, dtype=torch.int64).contiguous()
+    tl = torch.as_tensor(txt_len).to(device=dev, dtype=torch.int64).contiguous()
+    if el.numel() != B or tl.numel() != B:
+        raise _lib.AsrkError("rnnt_align: one enc_len and one txt_len per utterance")
+    alpha = beta = nll = None
+    if lattice is not None:
+        alpha, beta, nll = lattice
+        for a in (alpha, beta):
+            if a.shape != lpb.shape or a.dtype != torch.float32 or a.device != dev or not a.is_contiguous():
+                raise _lib.AsrkError("rnnt_align: lattice alpha / beta must be contiguous f32 [B, T, U + 1] on lpb's device")
+        if nll.shape != (B,) or nll.dtype != torch.float32 or nll.device != dev or not nll.is_contiguous():
+            raise _lib.AsrkError("rnnt_align: lattice nll must be f32 [B] on lpb's device")
+    if stamps is not None and (stamps.shape != (B, 4) or stamps.dtype != torch.int64 or stamps.device != dev
+                               or not stamps.is_contiguous()):
+        raise _lib.AsrkError("rnnt_align: stamps must be a contiguous int64 [B, 4] tensor on lpb's device")
+    frames = torch.empty((B, U1 - 1), dtype=torch.int32, device=dev)
+    done = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tok_logp = torch.empty((B, U1 - 1), dtype=torch.float32, device=dev)
+    tok_post = torch.empty((B, U1 - 1), dtype=torch.float32, device=dev) if lattice is not None else None
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    need = L.asrk_rnnt_align_ws_bytes(B, T, U1, flags)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+    _lib.check(L.asrk_rnnt_align_f32(_p(lpb), _p(lpl), _p(el), _p(tl), B, T, U1, flags, _p(alpha), _p(beta), _p(nll),
+                                     _p(frames), _p(done), _p(tok_logp), _p(tok_post), _p(score), _p(stamps), _p(ws),
+                                     need, _stream()), "rnnt_align")
+    return RNNTAlignment(frames, done, tok_logp, tok_post, score)
+
+
 RNNTGreedyState = collections.namedtuple("RNNTGreedyState",
                                          ["t_ptr", "n_sym", "n_tok", "tokens", "last_tok", "emit", "done"])
 

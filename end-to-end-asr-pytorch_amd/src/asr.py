@@ -133,6 +133,22 @@ class ASR(nn.Module):
         return tokens, n_tok, score, n_hyp, encode_len
 
     @torch.no_grad()
+    def transducer_align(self, audio_feature, feature_len, txt, txt_len, confidence=False, max_logits_bytes=1 << 30,
+                         packed=False):
+        ''' Forced alignment of every utterance to its transcript with the transducer head: encoder ->
+            TransducerHead.lattice_logp (at most max_logits_bytes of joint logits at a time) -> optionally the alpha /
+            beta lattice -> ops.rnnt_align (the best path, found and traced back on the device).  txt [B,U] padded
+            token ids, txt_len [B].  Returns (frames [B,U], labels_done [B,T'], tok_logp [B,U], tok_post [B,U] or None
+            without confidence, score [B], encode_len [B]): frames are ENCODER frames; tokens >= txt_len[b] and frames
+            >= encode_len[b] hold -1; a score of -inf means the transcript does not fit.  packed=True (needs
+            encoder.supports_packed()): every utterance is encoded as if alone and unpadded, as in ctc_align. '''
+        self._need_transducer('transducer_align')
+        encode_feature, encode_len = self.encoder(audio_feature, feature_len, packed=packed)
+        al = self.transducer.align(encode_feature, encode_len, txt, txt_len, confidence=confidence,
+                                   max_logits_bytes=max_logits_bytes)
+        return al.frames, al.labels_done, al.tok_logp, al.tok_post, al.score, encode_len
+
+    @torch.no_grad()
     def ctc_align(self, audio_feature, feature_len, txt, txt_len, packed=False):
         ''' Forced alignment of every utterance to its transcript with the CTC head: encoder -> CTC head ->
             log_softmax -> ops.ctc_align (the best CTC path, found and traced back on the device).  txt [B,L] padded

@@ -4,6 +4,8 @@ a ReLU; csrc/rnnt_ctx.hip), joint network tanh(lin_enc(enc)[b,t] + lin_pred(pred
 logits for ops.RNNTLoss, and batched greedy decoding with device-resident bookkeeping (csrc/rnnt.hip) and an
 alignment-length-synchronous beam search with merged alignments and n-gram LM fusion (csrc/rnnt_beam.hip).
 Blank = <sos> = 0.
+Forced alignment (lattice_logp, align; csrc/rnnt_align.hip): the best path through the lattice gives every label its
+emission frame, log-probability and posterior.
 With the `prune:` sub-block the training loss is the pruned one (Kuang et al. 2022; csrc/rnnt_prune.hip): an additive
 joiner lin_am(enc)[b,t] + lin_lm(pred)[b,u] on the whole lattice picks `range` label positions per frame, and the joint
 network and the loss run on that band only.
@@ -96,17 +98,23 @@ def infeasible_utterances(enc_len, txt_len, prune_range):
 
 
 BEAM_KEYS = ('beam_size', 'nbest', 'lm_weight')
+ALIGN_KEYS = ('align', 'timestamps')
 
 
 def take_decode_block(dcfg):
     ''' removes `transducer` from the decode block (the parent solver hands the rest to the beam decoders) and returns
         {max_symbols, max_len_ratio} when it is enabled, else None.  The beam-search keys beam_size (1..32), nbest
         (1..beam_size) and lm_weight (>= 0) are validated and returned only when the block names them: beam_size > 1 or
-        lm_weight > 0 selects ASR.transducer_beam, and lm_weight > 0 needs an n-gram `decode.lm_path`. '''
+        lm_weight > 0 selects ASR.transducer_beam, and lm_weight > 0 needs an n-gram `decode.lm_path`.  The same holds
+        for the two booleans of the forced alignment (ASR.transducer_align; bin/align_rnnt.py): `align: true` aligns
+        every utterance to its reference transcript instead of searching (no beam_size > 1, no lm_weight > 0, no
+        timestamps beside it), `timestamps: true` aligns the best hypothesis of the search and writes its token times
+        beside the usual output. '''
     block = dcfg.pop('transducer', None) or {}
     if not isinstance(block, dict):
         raise ValueError('decode.transducer: expected a mapping, got %r' % (block,))
-    unknown = sorted(set(block) - {'enable', 'max_symbols', 'max_len_ratio'} - set(BEAM_KEYS), key=str)
+    unknown = sorted(set(block) - {'enable', 'max_symbols', 'max_len_ratio'} - set(BEAM_KEYS) - set(ALIGN_KEYS),
+                     key=str)
     if unknown:
         raise ValueError('decode.transducer: unknown key(s) {}'.format(unknown))
     if not block.get('enable', False):
@@ -136,6 +144,15 @@ def take_decode_block(dcfg):
         if not is_ngram_path(dcfg.get('lm_path')):
             raise ValueError('decode.transducer: lm_weight > 0 fuses an n-gram LM only: decode.lm_path must end in '
                              '.arpa, .arpa.gz or .ngram.npz, got {!r}'.format(dcfg.get('lm_path')))
+    for key in ALIGN_KEYS:
+        if key in block:
+            if not isinstance(block[key], bool):
+                raise ValueError('decode.transducer: {} must be true or false, got {!r}'.format(key, block[key]))
+            opts[key] = block[key]
+    if opts.get('align', False):
+        if beam_size > 1 or opts.get('lm_weight', 0.0) > 0 or opts.get('timestamps', False):
+            raise ValueError('decode.transducer: align aligns the reference transcripts without a search: it excludes '
+                             'beam_size > 1, lm_weight > 0 and timestamps')
     return opts
 
 
@@ -266,6 +283,45 @@ class TransducerHead(nn.Module):
         logits = ops.linear(H, self.lin_out.weight, self.lin_out.bias)
         pruned_nll = ops.RNNTBandLossFn.apply(logits, txt, encode_len, txt_len, s, P.shape[1], self.blank, 'mean', True)
         return pruned_nll, simple_nll.mean()
+
+    @torch.no_grad()
+    def lattice_logp(self, encode_feature, encode_len, txt, txt_len, max_logits_bytes=1 << 30):
+        ''' encode_feature [B,T',D], txt [B,U] padded labels, lengths [B] -> (lpb, lpl) f32 [B,T',U+1]: the
+            log-probabilities of blank and of label u + 1 at every lattice cell (zeros outside every lattice), without
+            ever holding more than max_logits_bytes of [.., V] logits (one utterance alone may always run).  The
+            prediction network runs once; then groups of consecutive utterances go through the joint, lin_out and the
+            row pass (ops.rnnt_rows), which writes into slices of the two outputs.  A row's lpb / lpl depend on that row
+            alone, so every grouping gives the same bits.  The pruned model's lin_am / lin_lm are not used. '''
+        dev = encode_feature.device
+        B, T, _ = encode_feature.shape
+        txt = torch.as_tensor(txt).to(device=dev, dtype=torch.int64).contiguous()
+        U1 = txt.shape[1] + 1
+        el = torch.as_tensor(encode_len).to(device=dev, dtype=torch.int64).contiguous()
+        tl = torch.as_tensor(txt_len).to(device=dev, dtype=torch.int64).contiguous()
+        E = ops.linear(encode_feature, self.lin_enc.weight, self.lin_enc.bias)
+        P = ops.linear(self._predict(txt), self.lin_pred.weight, self.lin_pred.bias)
+        lpb = torch.empty((B, T, U1), dtype=torch.float32, device=dev)
+        lpl = torch.empty((B, T, U1), dtype=torch.float32, device=dev)
+        group = max(1, int(max_logits_bytes) // (T * U1 * self.vocab_size * 4))
+        for b0 in range(0, B, group):
+            b1 = min(B, b0 + group)
+            H = ops.RNNTJointFn.apply(E[b0:b1], P[b0:b1])
+            logits = ops.linear(H, self.lin_out.weight, self.lin_out.bias)
+            ops.rnnt_rows(logits, txt[b0:b1], el[b0:b1], tl[b0:b1], self.blank, out=(lpb[b0:b1], lpl[b0:b1]))
+            del H, logits
+        return lpb, lpl
+
+    @torch.no_grad()
+    def align(self, encode_feature, encode_len, txt, txt_len, confidence=False, max_logits_bytes=1 << 30,
+              flags=ops.ALIGN_BP_AUTO):
+        ''' forced alignment of every utterance to txt: lattice_logp, then the best path through the lattice, found and
+            traced back on the device (ops.rnnt_align) -> ops.RNNTAlignment(frames [B,U], labels_done [B,T'], tok_logp
+            [B,U], tok_post [B,U] or None, score [B]).  Frames are encoder frames; among equal-scoring paths every
+            label is emitted as early as possible.  confidence=True also runs the alpha / beta lattice of the loss and
+            returns the posterior of every chosen emission as tok_post. '''
+        lpb, lpl = self.lattice_logp(encode_feature, encode_len, txt, txt_len, max_logits_bytes)
+        lattice = ops.rnnt_lattice(lpb, lpl, encode_len, txt_len) if confidence else None
+        return ops.rnnt_align(lpb, lpl, encode_len, txt_len, flags=flags, lattice=lattice)
 
     @torch.no_grad()
     def greedy(self, encode_feature, encode_len, max_symbols, max_len):

@@ -1411,6 +1411,40 @@ int asrk_rnnt_beam_select(const float *lpb, const float *val, const int32_t *lab
                           int32_t *fin_n, int32_t *fin_len, double *fin_score, int32_t *fin_tok, int64_t *parent,
                           int64_t *last_tok, int32_t *emit, int64_t *sel, int64_t *lm_sel, void *stream);
 
+/* ---- transducer forced alignment (csrc/rnnt_align.hip, csrc/rnnt_align.inc; TransducerHead.align) ----------------------
+ * The best (Viterbi) path of every utterance through its lattice, on the lpb / lpl [B,T,U1] arrays of
+ * asrk_rnnt_rows_f32 (lengths clamped as there; cells outside an utterance's lattice are never read):
+ *   delta(0,0) = 0;  a = delta(t-1,u) + lpb(t-1,u) (t > 0, else -inf);  b = delta(t,u-1) + lpl(t,u-1) (u > 0, else -inf);
+ *   the label arc is taken iff (b > a) or (b != b);  delta(t,u) = taken ? b : a;
+ *   score[b] = delta(T_b-1,U_b) + lpb(T_b-1,U_b),
+ * in plain f32 (one add per arc, one compare per cell: a host f32 computation in this order gives the same bits).  Ties
+ * go to the blank arc: among equal-scoring paths every label is emitted as early as possible.  A NaN on an arc (lpl of
+ * a label outside [0,V)) reaches the score.
+ * Outputs (device): frames int32 [B,U1-1] = the frame at which y_{u+1} was emitted, -1 for u >= U_b; labels_done int32
+ * [B,T] = the number of labels emitted through frame t (the u at which frame t's blank was taken), -1 for t >= T_b;
+ * tok_logp [B,U1-1] = lpl at the emitting cell, 0 beyond U_b; score [B] = the best path's log-probability.  With alpha,
+ * beta, nll (asrk_rnnt_lattice_f32's, on the same lpb / lpl; all three or none) also tok_post [B,U1-1] = the posterior
+ * exp(((alpha + lpl) + beta(t,u+1)) + nll) of the chosen emission arc, 0 beyond U_b; without them tok_post is not
+ * touched.  An utterance whose score is -inf or NaN gets -1 in frames and labels_done and 0 in tok_logp and tok_post.
+ * One 128-lane workgroup per utterance walks the T_b + U_b anti-diagonals with the previous diagonal in LDS; lattice,
+ * backtrace and outputs run in one launch, nothing returns to the host.  Backpointers are one bit per cell, stored as
+ * one 64-bit ballot word per (diagonal, 64-label slot): (T + U1 - 1) * ceil(U1 / 64) words per utterance.  `flags`
+ * (ASRK_ALIGN_BP_*, above) picks where they live: _LDS in LDS when those words fit 128 KiB (beside at most 16 KiB of
+ * diagonals), ASRK_ESHAPE otherwise; _GLOBAL in the caller's workspace; _AUTO (0) LDS where it fits.
+ * ws: caller-owned device memory, 16-byte aligned, at least asrk_rnnt_align_ws_bytes(B, T, U1, flags) bytes, private to
+ * the call until the stream has passed it; the size is 0 on the LDS route (ws may be NULL) and for arguments the call
+ * rejects.  stamps: optional (NULL allowed) int64 [B,4], device wall-clock ticks of utterance b's workgroup at its
+ * start, after the lattice, after the backtrace and at its end (tools/rnnt_align_bench.py).
+ * ASRK_EINVAL, before any device call: a NULL pointer (frames, tok_logp, tok_post may be NULL when U1 == 1), B < 0, T or
+ * U1 <= 0, unknown flags, only some of alpha / beta / nll, a NULL, misaligned or short workspace.  ASRK_ESHAPE:
+ * U1 > 2048, B*T*U1 > INT32_MAX, a forced LDS route that does not fit.  B == 0: ASRK_OK without a launch.
+ * Call site: ops.rnnt_align. */
+size_t asrk_rnnt_align_ws_bytes(int B, int T, int U1, int flags);
+int asrk_rnnt_align_f32(const float *lpb, const float *lpl, const int64_t *enc_len, const int64_t *txt_len, int B, int T,
+                        int U1, int flags, const float *alpha, const float *beta, const float *nll, int32_t *frames,
+                        int32_t *labels_done, float *tok_logp, float *tok_post, float *score, int64_t *stamps, void *ws,
+                        size_t ws_bytes, void *stream);
+
 /* ---- CTC prefix scores for joint CTC-attention beam search (src/ctc.py:76-116) -----------
  * All (hypothesis h, candidate c) pairs of one beam step in one launch.  x [T,V] log-probs;
  * r_prev [n,T,2] (0 = non-blank, 1 = blank path) of each hypothesis' prefix g_h; prefix_len[h] =
