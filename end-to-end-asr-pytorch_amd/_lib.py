@@ -64,6 +64,11 @@ SIGNATURES = {
                                                c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "asrk_ngram_step_f32": (c_int, [c_int] * 4 + [c_vp] * 8 + [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64,
                                     c_int, c_vp]),
+    "asrk_bias_step_f32": (c_int, [c_int] * 3 + [c_vp] * 7 + [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int,
+                                   c_vp]),
+    "asrk_ngram_bias_step_f32": (c_int, [c_int] * 4 + [c_vp] * 8 + [c_int] * 2 + [c_vp] * 7
+                                 + [c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp]),
+    "asrk_bias_walk": (c_int, [c_int] * 3 + [c_vp] * 7 + [c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "asrk_fbank_frames_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_int,
                                       c_vp]),
     "asrk_power_spectrum_f32": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),

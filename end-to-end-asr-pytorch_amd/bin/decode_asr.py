@@ -34,6 +34,12 @@ Two booleans of the block give token times (bin/align_rnnt.py): `align: true` tu
 alignment of both sets to their reference transcripts (no search, no LM; `..._rnnt_align.tsv` and
 `..._rnnt_align_score.tsv`), `timestamps: true` force-aligns the best hypothesis of the greedy or beam search and writes
 `..._rnnt_times.tsv` beside the usual files, which stay byte for byte what they are without the key.
+
+The optional block `decode: {bias: {path: PHRASES.txt | LIST.bias.npz, weight: 1.5}}` boosts a list of phrases in the
+joint CTC-attention search, the CTC prefix search and the transducer beam search (src/bias.py: contextual biasing), alone
+or fused with the n-gram LM of `decode.lm_path`; with `decode.transducer` it selects the beam search even at
+`beam_size: 1`.  The block never reaches the beam decoders' keyword arguments.  It is refused at set-up with an RNN-LM,
+with `rescore`, with transducer `align` and with greedy CTC / attention decoding.  Without the block nothing here changes.
 """
 import os
 
@@ -41,6 +47,7 @@ from . import align_asr, align_rnnt, test_asr
 from ..parallel import gather_in_order
 from ..src.rescore import RescoreDecoder, check_decode_config
 from ..src.transducer import take_decode_block, uses_beam
+from ..src.bias import BiasedNGram, ContextBias, check_bias_config, install_bias, take_bias_block, tokenizer_encode
 
 
 class _FusedGreedy:
@@ -62,8 +69,14 @@ class Solver(test_asr.Solver):
         # loaders, one output file per set), whatever decode.beam_size says: the transducer searches are batched and take
         # their own beam_size from the block
         self.transducer = take_decode_block(config['decode'])
+        # contextual biasing (src/bias.py): taken out of the block as well; the combinations it excludes stop the run here
+        self.bias_cfg = take_bias_block(config['decode'])
+        check_bias_config(config['decode'], self.bias_cfg, transducer=self.transducer,
+                          greedy=not self.transducer and not self.align and config['decode'].get('beam_size') == 1)
         if self.transducer:
             config['decode']['beam_size'] = 1       # (the parent's; the transducer's own is self.transducer['beam_size'])
+            if self.bias_cfg:
+                self.transducer['bias'] = True      # selects the beam search, as lm_weight > 0 does (uses_beam)
         check_decode_config(config['decode'], config.get('emb'))
         # taken out of the block: the parent hands the whole decode block to BeamDecoder(**dcfg)
         rescore = config['decode'].pop('rescore', None) or {}
@@ -96,10 +109,19 @@ class Solver(test_asr.Solver):
                 return
             if uses_beam(self.transducer):
                 opts = self.transducer
+                self.transducer_lm_weight = opts.get('lm_weight', 0.0)
                 if opts.get('lm_weight', 0.0) > 0:
                     from ..src.ngram import NGramLM
                     self.transducer_lm = NGramLM.from_file(self.config['decode']['lm_path'],
                                                            self.vocab_size).to(self.device)
+                bias = self.context_bias()
+                if bias is not None and self.transducer_lm is not None:
+                    self.transducer_lm = BiasedNGram.pair(self.transducer_lm, bias, opts['lm_weight'])
+                elif bias is not None:
+                    self.transducer_lm, self.transducer_lm_weight = bias, 1.0     # its rows are added as they are
+                if bias is not None:
+                    self.verbose(['Decode spec| Transducer beam search with contextual biasing']
+                                 + self.transducer_lm.create_msg())
                 self.verbose(['Decode spec| Transducer beam search \t| Beam size = {} | N-best = {} | LM weight = {} | '
                               'Max symbols per frame = {} | Max len ratio = {}'.format(
                                   opts.get('beam_size', 1), opts.get('nbest', 1), opts.get('lm_weight', 0.0),
@@ -128,12 +150,26 @@ class Solver(test_asr.Solver):
             if self.greedy and self.emb_decoder is not None:
                 # the parent's greedy pass calls self.decoder(feat, feat_len, steps): the model, with the plug-in bound
                 self.decoder = _FusedGreedy(self.model, self.emb_decoder)
+            bias = self.context_bias()
+            if bias is not None:
+                # the parent built the beam decoder from the decode block, which no longer holds `bias`: the ContextBias
+                # takes its scorer slot here (alone, or fused with the n-gram LM the parent loaded)
+                install_bias(self.decoder, bias, self.device)
+                self.verbose(self.decoder.lm.create_msg())
             return
         # alignment needs the acoustic model only: no search, no LM
         init_adadelta = self.config['hparas']['optimizer'] == 'Adadelta'
         self.model = test_asr.ASR(self.feat_dim, self.vocab_size, init_adadelta,
                                   **self.config['model']).to(self.device)
         self.load_ckpt()        # eval mode
+
+    def context_bias(self):
+        ''' the ContextBias of the `decode.bias` block (phrases encoded with the model's own text encoder), or None '''
+        cfg = getattr(self, 'bias_cfg', None)
+        if not cfg:
+            return None
+        return ContextBias.from_file(cfg['path'], self.vocab_size, weight=cfg['weight'],
+                                     encode=tokenizer_encode(self.tokenizer)).to(self.device)
 
     def load_ckpt(self):
         ''' the parent's set_model calls this between building the model and building the decoder: the place where the
@@ -160,7 +196,8 @@ class Solver(test_asr.Solver):
                 opts = self.transducer
                 tokens, n_tok, score, n_hyp, _ = self.model.transducer_beam(
                     feat, feat_len, opts.get('beam_size', 1), opts['max_symbols'], opts['max_len_ratio'],
-                    nbest=opts.get('nbest', 1), lm=self.transducer_lm, lm_weight=opts.get('lm_weight', 0.0))
+                    nbest=opts.get('nbest', 1), lm=self.transducer_lm,
+                    lm_weight=getattr(self, 'transducer_lm_weight', opts.get('lm_weight', 0.0)))
                 tokens, n_tok, score, n_hyp = tokens.tolist(), n_tok.tolist(), score.tolist(), n_hyp.tolist()
                 for j in range(len(txt)):
                     idx = j + self.config['data']['corpus']['batch_size'] * i

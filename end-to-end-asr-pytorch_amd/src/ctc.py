@@ -164,7 +164,7 @@ class CTCBeamDecoder(nn.Module):
     ''' Beam decoder for ASR (CTC only) (reference: src/ctc.py:210-352) '''
 
     def __init__(self, asr, vocab_range, beam_size, vocab_candidate,
-                 lm_path='', lm_config='', lm_weight=0.0, device=None):
+                 lm_path='', lm_config='', lm_weight=0.0, device=None, bias=None):
         super().__init__()
         self.asr = asr
         self.vocab_range = list(vocab_range)
@@ -186,11 +186,20 @@ class CTCBeamDecoder(nn.Module):
                 self.lm = RNNLM(self.asr.vocab_size, **lm_config['model']).to(self.device)
                 self.lm.load_state_dict(torch.load(self.lm_path, map_location='cpu')['model'])
             self.lm.eval()
+        # contextual biasing (src/bias.py): a ContextBias takes the scorer slot, alone (weight exactly 1) or fused with
+        # the n-gram; without it nothing above changes.  The search returns no scores, so the pending bonus of a
+        # hypothesis that stops inside a phrase stays in its internal ranking.
+        self.bias = bias
+        if bias is not None:
+            self.device = device
+            from .bias import attach_bias
+            attach_bias(self, bias)
+            self.lm.to(self.device)
 
     def create_msg(self):
         msg = ['Decode spec| CTC decoding \t| Beam size = {} \t| LM weight = {}'.format(
-            self.beam_size, self.lm_w)]
-        if self.apply_lm and isinstance(self.lm, NGramLM):
+            self.beam_size, self.lm_w if self.bias is None else getattr(self, 'lm_w_config', 0))]
+        if self.apply_lm and (isinstance(self.lm, NGramLM) or self.bias is not None):
             msg += self.lm.create_msg()
         return msg
 

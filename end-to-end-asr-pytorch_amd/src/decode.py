@@ -23,6 +23,7 @@ from .. import gru_ops
 from .. import speller_ops as sops
 from .lm import RNNLM
 from .ngram import NGramLM, is_ngram_path
+from .bias import attach_bias
 from .ctc import CTCPrefixScore, LOG_ZERO
 
 CTC_BEAM_RATIO = 1.5   # (reference: src/decode.py:10)
@@ -32,7 +33,7 @@ class BeamDecoder(nn.Module):
     ''' Beam decoder for ASR (reference: src/decode.py:13-173) '''
 
     def __init__(self, asr, emb_decoder, beam_size, min_len_ratio, max_len_ratio,
-                 lm_path='', lm_config='', lm_weight=0.0, ctc_weight=0.0):
+                 lm_path='', lm_config='', lm_weight=0.0, ctc_weight=0.0, bias=None):
         super().__init__()
         self.beam_size = beam_size
         self.min_len_ratio = min_len_ratio
@@ -57,6 +58,11 @@ class BeamDecoder(nn.Module):
                 self.lm = RNNLM(self.asr.vocab_size, **lm_config['model'])
                 self.lm.load_state_dict(torch.load(self.lm_path, map_location='cpu')['model'])
             self.lm.eval()
+        # contextual biasing (src/bias.py): a ContextBias takes the scorer slot, alone (weight exactly 1) or fused with
+        # the n-gram; without it nothing above changes
+        self.bias = bias
+        if bias is not None:
+            attach_bias(self, bias)
 
         self.apply_emb = emb_decoder is not None
         if self.apply_emb:
@@ -73,11 +79,13 @@ class BeamDecoder(nn.Module):
             self.beam_size, self.min_len_ratio, self.max_len_ratio)]
         if self.apply_ctc:
             msg.append('           |Joint CTC decoding enabled \t| weight = {:.2f}\t'.format(self.ctc_w))
-        if self.apply_lm:
+        if self.apply_lm and self.lm_path:
             msg.append('           |Joint LM decoding enabled \t| weight = {:.2f}\t| src = {}'.format(
                 self.lm_w, self.lm_path))
             if isinstance(self.lm, NGramLM):
                 msg += self.lm.create_msg()
+        if self.bias is not None:
+            msg += self.lm.create_msg()
         if self.apply_emb:
             msg.append('           |Joint Emb. decoding enabled \t| weight = {:.2f}'.format(
                 self.emb_decoder.fuse_lambda.mean().cpu().item()))

@@ -158,7 +158,7 @@ def take_decode_block(dcfg):
 
 def uses_beam(opts):
     ''' the decode block (take_decode_block's result) asks for the beam search rather than the greedy one '''
-    return bool(opts) and (opts.get('beam_size', 1) > 1 or opts.get('lm_weight', 0.0) > 0)
+    return bool(opts) and (opts.get('beam_size', 1) > 1 or opts.get('lm_weight', 0.0) > 0 or bool(opts.get('bias')))
 
 
 class TransducerHead(nn.Module):
@@ -405,7 +405,9 @@ class TransducerHead(nn.Module):
             lp + lm_weight * lm; csrc/rnnt_beam.hip) and one select launch (candidates, merge of equal sequences, cut to
             W, finished list); then the survivors' states are gathered from their parents, the cells, lin_pred and the
             LM step on the appended token, and the stepped state is kept where a token was appended.  Nothing is read
-            back inside the loop.  lm: an NGramLM (its log-probabilities are added to the labels, never to blank). '''
+            back inside the loop.  lm: an NGramLM (its log-probabilities are added to the labels, never to blank), a
+            ContextBias (src/bias.py; lm_weight 1.0) or a BiasedNGram; with biasing the pending bonus of a hypothesis that
+            stops inside a phrase is taken back after the loop and the finished lists are re-sorted (_bank_bias). '''
         nbest, max_len = int(nbest), int(max_len)
         if not 1 <= nbest <= int(beam_size):
             raise ValueError('beam_search: 1 <= nbest <= beam_size, got nbest = {}'.format(nbest))
@@ -415,25 +417,43 @@ class TransducerHead(nn.Module):
         dev = encode_feature.device
         B, T, _ = encode_feature.shape
         f = (T + max_len) & 1                       # the buffer the last iteration wrote
+        fin_tok, fin_len, fin_score = st.fin_tok[f], st.fin_len[f], st.fin_score[f]
+        if lm is not None and float(lm_weight) > 0 and hasattr(lm, 'walk'):
+            fin_tok, fin_len, fin_score = self._bank_bias(lm, lm_weight, fin_tok, fin_len, fin_score, st.fin_n[f])
         tokens = torch.zeros((B, nbest, max_len), dtype=torch.int64, device=dev)
-        n_tok = st.fin_len[f][:, :nbest].clone()
+        n_tok = fin_len[:, :nbest].clone()
         valid = torch.arange(nbest, device=dev).view(1, nbest) < st.fin_n[f].view(B, 1)
         n_tok = torch.where(valid, n_tok, torch.zeros_like(n_tok))
         if max_len > 0:
             pos = torch.arange(max_len, device=dev).view(1, 1, max_len)
-            tokens = torch.where(pos < n_tok.unsqueeze(2), st.fin_tok[f][:, :nbest, :max_len].to(torch.int64), tokens)
-        score = torch.where(valid, st.fin_score[f][:, :nbest], torch.full_like(st.fin_score[f][:, :nbest], float('-inf')))
+            tokens = torch.where(pos < n_tok.unsqueeze(2), fin_tok[:, :nbest, :max_len].to(torch.int64), tokens)
+        score = torch.where(valid, fin_score[:, :nbest], torch.full_like(fin_score[:, :nbest], float('-inf')))
         return tokens, n_tok, score, torch.clamp(st.fin_n[f], max=nbest)
+
+    @staticmethod
+    def _bank_bias(lm, lm_weight, fin_tok, fin_len, fin_score, fin_n):
+        ''' contextual biasing: a finished hypothesis that stops inside a phrase still holds the phrase's pending bonus
+            (ContextBias.walk's residual, in the row's units: times lm_weight).  It is taken back and each utterance's
+            finished list [B, W] re-sorted best first (stable: equal scores keep their order), all on the device. '''
+        B, W, Lc = fin_tok.shape
+        _, _, residual = lm.walk(fin_tok.reshape(B * W, Lc), torch.clamp(fin_len.reshape(B * W), min=0, max=Lc))
+        valid = torch.arange(W, device=fin_tok.device).view(1, W) < fin_n.view(B, 1)
+        score = fin_score - residual.view(B, W).to(torch.float64) * float(lm_weight)
+        score = torch.where(valid, score, torch.full_like(score, float('-inf')))
+        order = torch.sort(score, dim=1, descending=True, stable=True)[1]
+        return (torch.gather(fin_tok, 1, order.view(B, W, 1).expand(B, W, Lc)), torch.gather(fin_len, 1, order),
+                torch.gather(score, 1, order))
 
     @torch.no_grad()
     def beam_steps(self, encode_feature, encode_len, beam_size, max_symbols, max_len, lm=None, lm_weight=0.0):
         ''' the loop of beam_search as a generator: yields (i, state) after iteration i = 0 .. T' + max_len - 1, `state`
             the ops.RNNTBeamState whose buffer 1 - (i & 1) iteration i has just written (the next beam and the finished
             list so far).  Nothing is read back; a caller that stops early leaves the search unfinished. '''
+        from .bias import BiasedNGram, ContextBias
         from .ngram import NGramLM
-        if lm is not None and not isinstance(lm, NGramLM):
-            raise NotImplementedError('TransducerHead.beam_search fuses an NGramLM only, got {}'.format(
-                type(lm).__name__))
+        if lm is not None and not isinstance(lm, (NGramLM, ContextBias, BiasedNGram)):
+            raise NotImplementedError('TransducerHead.beam_search fuses an NGramLM (with or without a ContextBias) or a '
+                                      'ContextBias only, got {}'.format(type(lm).__name__))
         dev = encode_feature.device
         B, T, _ = encode_feature.shape
         W, max_symbols, max_len = int(beam_size), int(max_symbols), int(max_len)
@@ -480,7 +500,8 @@ class TransducerHead(nn.Module):
         if use_lm:
             # LM rows and the int32 LM state (moved as 4-byte rows): [kept | stepped], two such buffers in turn
             lm_rows = [torch.zeros((2, R, V), dtype=torch.float32, device=dev) for _ in range(2)]
-            lm_state = [torch.zeros((2, R, 1), dtype=torch.float32, device=dev) for _ in range(2)]
+            S = int(getattr(lm, 'state_width', 1))       # int32 per row: 1 (n-gram or bias), 2 (both)
+            lm_state = [torch.zeros((2, R, S), dtype=torch.float32, device=dev) for _ in range(2)]
             lm(st.last_tok.view(R, 1), None, None, out=lm_rows[0][0], state_out=lm_state[0][0].view(torch.int32))
         table = (st.lse, st.lpb, st.val, st.lab)
         k = 0
@@ -500,7 +521,7 @@ class TransducerHead(nn.Module):
                 lm(st.last_tok.view(R, 1), None, lm_state[k][0].view(torch.int32), parent=st.parent,
                    out=lm_rows[k][1], state_out=lm_state[k][1].view(torch.int32))
                 dops.gather_rows_multi([(lm_rows[k], lm_rows[1 - k][0], V, 1, False),
-                                        (lm_state[k], lm_state[1 - k][0], 1, 1, False)], st.lm_sel)
+                                        (lm_state[k], lm_state[1 - k][0], S, 1, False)], st.lm_sel)
                 k = 1 - k
             yield i, st
 
@@ -514,7 +535,8 @@ class TransducerHead(nn.Module):
         R = B * W
         if lm is not None:
             lm_rows = [torch.zeros((2, R, V), dtype=torch.float32, device=dev) for _ in range(2)]
-            lm_state = [torch.zeros((2, R, 1), dtype=torch.float32, device=dev) for _ in range(2)]
+            S = int(getattr(lm, 'state_width', 1))       # int32 per row: 1 (n-gram or bias), 2 (both)
+            lm_state = [torch.zeros((2, R, S), dtype=torch.float32, device=dev) for _ in range(2)]
             lm(st.last_tok.view(R, 1), None, None, out=lm_rows[0][0], state_out=lm_state[0][0].view(torch.int32))
         table = (st.lse, st.lpb, st.val, st.lab)
         P = self._ctx_rows(st.tokens[0], st.n_tok[0])
@@ -531,7 +553,7 @@ class TransducerHead(nn.Module):
                 lm(st.last_tok.view(R, 1), None, lm_state[k][0].view(torch.int32), parent=st.parent,
                    out=lm_rows[k][1], state_out=lm_state[k][1].view(torch.int32))
                 dops.gather_rows_multi([(lm_rows[k], lm_rows[1 - k][0], V, 1, False),
-                                        (lm_state[k], lm_state[1 - k][0], 1, 1, False)], st.lm_sel)
+                                        (lm_state[k], lm_state[1 - k][0], S, 1, False)], st.lm_sel)
                 k = 1 - k
             yield i, st
 

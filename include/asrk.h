@@ -425,6 +425,45 @@ int asrk_ngram_step_f32(int order, int V, int n_nodes, int n_entries, const floa
                         int n_state, const int64_t *token, const void *parent, int parent_is_i64, int32_t *state_out,
                         float *out, int64_t row_stride, int R, void *stream);
 
+/* ---- contextual biasing: a phrase-boosting automaton behind the same row contract (no counterpart in the reference) ----
+ * An Aho-Corasick automaton over the model's tokens, built by src/bias.py: build_image (node 0 = the root):
+ *     phi [n_nodes] f32: the pending (not yet banked) bonus of a node, phi[0] = 0;
+ *     root_arrive [V] f32, root_next [V] int32: arrive[goto(0, v)] and goto(0, v), dense;
+ *     ext_off [n_nodes + 1] int32 (CSR; node 0 has no entries); ext_word (strictly ascending inside a node), ext_arrive,
+ *     ext_next [n_entries]: for node n >= 1 the children of every node on its fail chain except the root, merged so
+ *     that the deepest node wins.  The three ext_* arrays may be NULL when n_entries == 0.
+ *   goto(s, v): the entry of s that holds v, else (root_next[v], root_arrive[v]); a token outside [0, V) leads to the
+ *     root with arrive 0.  delta(s, v) = fl(arrive[goto(s, v)] - phi[s]): one f32 subtraction of two stored values.
+ * asrk_bias_step_f32: row r continues state_in[parent ? parent[r] : r] (state_in == NULL or a parent outside
+ *   [0, n_state): the root), consumes token[r], writes its new state s' to state_out[r] and delta(s', v) to
+ *   out[r * row_stride + v] for v < V (columns V .. row_stride - 1 are not touched).  One workgroup per row.
+ * asrk_ngram_bias_step_f32: the n-gram step of asrk_ngram_step_f32 and the biasing step in one launch that writes the
+ *   row once.  States are int32 pairs (n-gram node, automaton node): state_in [n_state, 2], state_out [R, 2].
+ *   out[v] = fl(L(v) + delta(s', v)) with L(v) bit for bit what asrk_ngram_step_f32 writes: one f32 add, no multiply.
+ * asrk_bias_walk: sequence h = tokens[h * token_stride + i], i < min(max(n_tok[h], 0), L), walked from the root:
+ *   state[h] = the final node, total[h] = the f32 sum of its deltas in token order, residual[h] = phi[state[h]].
+ * token(s) int64; parent [R] int32, or int64 when parent_is_i64 != 0, or NULL; state_out must not be state_in.
+ * ASRK_EINVAL, checked before any device call: V <= 0, n_nodes < 1, a negative count, a NULL image array (ext_* only
+ * when n_entries > 0), row_stride < V, token_stride < L, the n-gram conditions of asrk_ngram_step_f32; for R > 0 (H > 0)
+ * also a NULL token / state / output array and state_out == state_in.  R == 0 (H == 0) is ASRK_OK. */
+int asrk_bias_step_f32(int V, int n_nodes, int n_entries, const float *phi, const float *root_arrive,
+                       const int32_t *root_next, const int32_t *ext_off, const int32_t *ext_word,
+                       const float *ext_arrive, const int32_t *ext_next, const int32_t *state_in, int n_state,
+                       const int64_t *token, const void *parent, int parent_is_i64, int32_t *state_out, float *out,
+                       int64_t row_stride, int R, void *stream);
+int asrk_ngram_bias_step_f32(int order, int V, int n_nodes, int n_entries, const float *uni_logp,
+                             const int32_t *uni_next, const float *bo, const int32_t *fail, const int32_t *child_off,
+                             const int32_t *word, const float *logp, const int32_t *next, int b_nodes, int b_entries,
+                             const float *phi, const float *root_arrive, const int32_t *root_next,
+                             const int32_t *ext_off, const int32_t *ext_word, const float *ext_arrive,
+                             const int32_t *ext_next, const int32_t *state_in, int n_state, const int64_t *token,
+                             const void *parent, int parent_is_i64, int32_t *state_out, float *out, int64_t row_stride,
+                             int R, void *stream);
+int asrk_bias_walk(int V, int n_nodes, int n_entries, const float *phi, const float *root_arrive,
+                   const int32_t *root_next, const int32_t *ext_off, const int32_t *ext_word, const float *ext_arrive,
+                   const int32_t *ext_next, const int64_t *tokens, int64_t token_stride, const int32_t *n_tok, int L,
+                   int H, int32_t *state, float *total, float *residual, void *stream);
+
 /* ---- attention decoder step (src/module.py:179-258, src/asr.py:277-313) -------------------
  * BN = B*num_head rows ordered (b, head).  All tensors contiguous f32; lens int64 [B].
  * loc_conv:  c[b,t,k] = sum_{n,j} prev_att[b,n,t+j-ks] * Wc[k,n,j]   (Conv1d(N,K,2ks+1,pad ks))
