@@ -6,11 +6,10 @@
 #include "common.h"
 #include "knobs.h"
 #include "philox.h"
+#include "rowops_plan.h"
 #include <algorithm>
 
 namespace {
-
-static inline bool al16h(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
 // ---------------------------------------------------------------- LayerNorm
 // one wave per row; biased variance, eps inside the sqrt (torch.nn.LayerNorm semantics)
@@ -163,13 +162,9 @@ extern "C" int asrk_layer_norm_bwd_f32(const float *x, const float *weight, cons
         hipLaunchKernelGGL(ln_bwd_data_kernel, dim3((unsigned)asrk_div_up(rows, 4)), dim3(256), 0, s,
                            x, weight, dy, mean, rstd, dx, rows, cols);
     if (dweight) {
-        // ASRK_DETERMINISTIC: one row chunk - a column's fixed-order block sum is the only value added to dw / db
-        const int chunks = asrk_knobs_().get(asrk_knobs_().deterministic, 0)
-                               ? 1 : std::max(1, std::min(asrk_div_up(rows, 64), 256));
-        const int rpc = asrk_div_up(asrk_div_up(rows, chunks), 4) * 4;
-        hipLaunchKernelGGL(ln_bwd_param_kernel,
-                           dim3((unsigned)asrk_div_up(cols, 64), (unsigned)asrk_div_up(rows, rpc)),
-                           dim3(256), 0, s, x, dy, mean, rstd, dweight, dbias, rows, cols, rpc);
+        const rowops_plan::LnParamPlan pl = rowops_plan::ln_param_plan(rows, cols);
+        hipLaunchKernelGGL(ln_bwd_param_kernel, dim3(pl.gx, pl.gy), dim3(256), 0, s, x, dy, mean, rstd, dweight, dbias,
+                           rows, cols, pl.rpc);
     }
     asrk_prof_end_(PROF_ROWOPS, s);
     ASRK_LAUNCH_CHECK();
@@ -184,11 +179,10 @@ extern "C" int asrk_dropout_f32(const float *x, float *y, int64_t n, float p, ui
     hipStream_t s = (hipStream_t)stream;
     const uint32_t thresh24 = (uint32_t)llrintf(p * 16777216.0f);
     const float scale = 1.0f / (1.0f - p);
-    const bool vec = al16h(x) && al16h(y) && (n % 4 == 0);
-    const int64_t nq = (n + 3) / 4;
-    const unsigned grid = (unsigned)std::min<int64_t>(8192, asrk_div_up64(nq, 256));
+    const rowops_plan::DropoutPlan pl = rowops_plan::dropout_plan(x, y, n);
+    const unsigned grid = pl.grid;
     asrk_prof_begin_(PROF_ROWOPS, s);
-    if (vec)
+    if (pl.variant == 1)
         hipLaunchKernelGGL((dropout_kernel<true>), dim3(grid), dim3(256), 0, s, x, y, n, thresh24,
                            scale, (uint64_t)seed, (uint64_t)offset);
     else

@@ -5,6 +5,7 @@
 // scalar so the separate "scale all gradients" pass disappears.  Arithmetic order follows
 // torch/optim/adadelta.py / adam.py (single-tensor path, weight_decay = 0, maximize = False).
 #include "common.h"
+#include "rowops_plan.h"
 #include <algorithm>
 
 namespace {
@@ -128,8 +129,14 @@ int multi_launch(int count, float *const *params, const float *const *grads, flo
                  hipStream_t s) {
     // `t` is the consumed-tensor cursor: empty tensors are skipped without taking a table slot, so a
     // chunk may span more than MT_MAX entries and the next chunk starts exactly where this one ended
+    // the whole table is checked before the first launch: an invalid entry beyond the first chunk must not leave the
+    // chunks before it stepped
+    for (int t = 0; t < count; ++t) {
+        if (numel[t] < 0) return ASRK_EINVAL;
+        if (numel[t] > 0 && (!params[t] || !grads[t] || !st0[t] || !st1[t])) return ASRK_EINVAL;
+    }
     double bytes = 0.0;
-    for (int t = 0; t < count; ++t) bytes += numel[t] > 0 ? 28.0 * (double)numel[t] : 0.0;   // read p, g, 2 states; write p, 2 states
+    for (int t = 0; t < count; ++t) bytes += 28.0 * (double)numel[t];   // read p, g, 2 states; write p, 2 states
     asrk_prof_work_(PROF_OPTIM, bytes);
     asrk_prof_begin_(PROF_OPTIM, s);
     for (int t = 0; t < count;) {
@@ -139,9 +146,7 @@ int multi_launch(int count, float *const *params, const float *const *grads, flo
         for (int j = 0; j < 8; ++j) a.h[j] = h[j];
         int blocks = 0;
         for (; t < count && a.count < MT_MAX; ++t) {
-            if (numel[t] < 0) return ASRK_EINVAL;
             if (numel[t] == 0) continue;
-            if (!params[t] || !grads[t] || !st0[t] || !st1[t]) return ASRK_EINVAL;
             const int k = a.count++;
             a.p[k] = params[t]; a.g[k] = grads[t]; a.s0[k] = st0[t]; a.s1[k] = st1[t];
             a.n[k] = numel[t];
@@ -213,10 +218,7 @@ inline int norm_blocks_of(int64_t n) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(asrk_div_up64(n, 2048), 1024));
 }
 
-inline unsigned grid_for(int64_t n) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(asrk_div_up64(n, 256), 4096));
-}
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline unsigned grid_for(int64_t n) { return rowops_plan::optim_grid_for(n); }
 
 }  // namespace
 
@@ -227,12 +229,12 @@ extern "C" int asrk_adadelta_step_f32(float *param, const float *grad, float *sq
     if (n == 0) return ASRK_OK;
     if (!param || !grad || !square_avg || !acc_delta) return ASRK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = al16(param) && al16(grad) && al16(square_avg) && al16(acc_delta) && (n % 4 == 0);
-    if (vec)
-        hipLaunchKernelGGL((adadelta_kernel<true>), dim3(grid_for(n / 4)), dim3(256), 0, s, param, grad,
+    const rowops_plan::AdadeltaPlan pl = rowops_plan::adadelta_plan(param, grad, square_avg, acc_delta, n);
+    if (pl.variant == 1)
+        hipLaunchKernelGGL((adadelta_kernel<true>), dim3(pl.grid), dim3(256), 0, s, param, grad,
                            square_avg, acc_delta, n, (float)lr, (float)rho, (float)(1.0 - rho), (float)eps, clip_coef);
     else
-        hipLaunchKernelGGL((adadelta_kernel<false>), dim3(grid_for(n)), dim3(256), 0, s, param, grad,
+        hipLaunchKernelGGL((adadelta_kernel<false>), dim3(pl.grid), dim3(256), 0, s, param, grad,
                            square_avg, acc_delta, n, (float)lr, (float)rho, (float)(1.0 - rho), (float)eps, clip_coef);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
@@ -294,11 +296,13 @@ extern "C" int asrk_grad_norm_multi_f32(int count, const float *const *grads, co
     if (count < 0 || (count > 0 && (!grads || !numel)) || (!norm_out && !coef_out)) return ASRK_EINVAL;
     if (!ws || ws_bytes < asrk_grad_norm_ws_bytes(count, numel) || (reinterpret_cast<uintptr_t>(ws) & 7) != 0)
         return ASRK_EWORKSPACE;
+    for (int t = 0; t < count; ++t)                     // the whole table before the first launch, as multi_launch
+        if (numel[t] < 0 || (numel[t] > 0 && !grads[t])) return ASRK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     double *partials = reinterpret_cast<double *>(ws);
     int total = 0;
     double bytes = 0.0;
-    for (int t = 0; t < count; ++t) bytes += numel[t] > 0 ? 4.0 * (double)numel[t] : 0.0;     // one read of every gradient
+    for (int t = 0; t < count; ++t) bytes += 4.0 * (double)numel[t];     // one read of every gradient
     asrk_prof_work_(PROF_OPTIM, bytes);
     asrk_prof_begin_(PROF_OPTIM, s);
     for (int t = 0; t < count;) {
@@ -306,9 +310,7 @@ extern "C" int asrk_grad_norm_multi_f32(int count, const float *const *grads, co
         a.count = 0;
         int blocks = 0;
         for (; t < count && a.count < MT_MAX; ++t) {
-            if (numel[t] < 0) return ASRK_EINVAL;
             if (numel[t] == 0) continue;
-            if (!grads[t]) return ASRK_EINVAL;
             const int k = a.count++;
             a.g[k] = grads[t]; a.n[k] = numel[t]; a.blk0[k] = blocks;
             blocks += norm_blocks_of(numel[t]);

@@ -5,6 +5,7 @@
 // lanes, wave64 shuffles for the row reductions, no LDS round trips.
 #include "common.h"
 #include "knobs.h"
+#include "rowops_plan.h"
 
 namespace {
 
@@ -681,45 +682,34 @@ extern "C" int asrk_copy3d_f32(const float *src, float *dst, int n0, int n1, int
     if (n0 == 0 || n1 == 0 || n2 == 0) return ASRK_OK;
     if (!src || !dst) return ASRK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = al16(src) && al16(dst) && (n2 % 4 == 0) && (ss0 % 4 == 0) && (ss1 % 4 == 0) &&
-                     (ds0 % 4 == 0) && (ds1 % 4 == 0);
-    const int64_t total = (int64_t)n0 * n1 * (vec ? n2 / 4 : n2);
-    const unsigned grid = grid_for(total, 256);
+    const rowops_plan::Copy3dPlan pl = rowops_plan::copy3d_plan(src, dst, n0, n1, n2, ss0, ss1, ds0, ds1, accumulate);
+    const dim3 g(pl.gx, pl.gy);
     asrk_prof_begin_(PROF_ROWOPS, s);
-    const int64_t rows64 = (int64_t)n0 * n1;
-    if (vec && n2 / 4 >= 64 && rows64 < (1ll << 30)) {
-        const int rows = (int)rows64, per_row = n2 / 4;
-        const int gx = asrk_div_up(per_row, 256);
-        int rpb = 16;                                   // rows per block: >= ~2k blocks when possible
-        while (rpb > 4 && (int64_t)gx * asrk_div_up(rows, rpb) < 2048) rpb >>= 1;
-        if (asrk_div_up(rows, rpb) > 65535) rpb = asrk_div_up(rows, 65535);
-        const dim3 g(gx, asrk_div_up(rows, rpb));
-        if (g.y <= 65535u) {
-            if (accumulate)
-                hipLaunchKernelGGL((copy3d_rows_kernel<true>), g, dim3(256), 0, s, src, dst, rows, n1,
-                                   per_row, ss0, ss1, ds0, ds1, rpb);
-            else
-                hipLaunchKernelGGL((copy3d_rows_kernel<false>), g, dim3(256), 0, s, src, dst, rows, n1,
-                                   per_row, ss0, ss1, ds0, ds1, rpb);
-            asrk_prof_end_(PROF_ROWOPS, s);
-            ASRK_LAUNCH_CHECK();
-            return ASRK_OK;
-        }
-    }
-    if (vec) {
-        if (accumulate)
-            hipLaunchKernelGGL((copy3d_kernel<true, true>), dim3(grid), dim3(256), 0, s, src, dst,
-                               n1, n2, ss0, ss1, ds0, ds1, total);
-        else
-            hipLaunchKernelGGL((copy3d_kernel<true, false>), dim3(grid), dim3(256), 0, s, src, dst,
-                               n1, n2, ss0, ss1, ds0, ds1, total);
-    } else {
-        if (accumulate)
-            hipLaunchKernelGGL((copy3d_kernel<false, true>), dim3(grid), dim3(256), 0, s, src, dst,
-                               n1, n2, ss0, ss1, ds0, ds1, total);
-        else
-            hipLaunchKernelGGL((copy3d_kernel<false, false>), dim3(grid), dim3(256), 0, s, src,
-                               dst, n1, n2, ss0, ss1, ds0, ds1, total);
+    switch (pl.variant) {
+    case 5:
+        hipLaunchKernelGGL((copy3d_rows_kernel<true>), g, dim3(256), 0, s, src, dst, pl.rows, n1, pl.per_row, ss0, ss1,
+                           ds0, ds1, pl.rpb);
+        break;
+    case 4:
+        hipLaunchKernelGGL((copy3d_rows_kernel<false>), g, dim3(256), 0, s, src, dst, pl.rows, n1, pl.per_row, ss0, ss1,
+                           ds0, ds1, pl.rpb);
+        break;
+    case 3:
+        hipLaunchKernelGGL((copy3d_kernel<true, true>), g, dim3(256), 0, s, src, dst, n1, n2, ss0, ss1, ds0, ds1,
+                           pl.total);
+        break;
+    case 2:
+        hipLaunchKernelGGL((copy3d_kernel<true, false>), g, dim3(256), 0, s, src, dst, n1, n2, ss0, ss1, ds0, ds1,
+                           pl.total);
+        break;
+    case 1:
+        hipLaunchKernelGGL((copy3d_kernel<false, true>), g, dim3(256), 0, s, src, dst, n1, n2, ss0, ss1, ds0, ds1,
+                           pl.total);
+        break;
+    default:
+        hipLaunchKernelGGL((copy3d_kernel<false, false>), g, dim3(256), 0, s, src, dst, n1, n2, ss0, ss1, ds0, ds1,
+                           pl.total);
+        break;
     }
     asrk_prof_end_(PROF_ROWOPS, s);
     ASRK_LAUNCH_CHECK();
@@ -734,34 +724,75 @@ extern "C" int asrk_colsum_f32(const float *X, int M, int N, int ldx, float *out
     hipStream_t s = (hipStream_t)stream;
     if (!accumulate) ASRK_HIP(hipMemsetAsync(out, 0, (size_t)N * 4, s));
     if (M == 0) return ASRK_OK;
-    const bool vec = al16(X) && (N % 4 == 0) && (ldx % 4 == 0);
-    if (vec && ldx == N && N <= 128 && 256 % (N / 4) == 0 && M >= 4096) {
-        const int64_t total4 = (int64_t)M * (N / 4);
-        // out[c] takes one atomic per block: 2048 blocks on 64 addresses took longer than the 131-MB read itself
-        int blocks = asrk_knobs_().get(asrk_knobs_().deterministic, 0) ? 1 : 512;
-        const int64_t per_block = asrk_div_up64(asrk_div_up64(total4, blocks), 2048) * 2048;
-        blocks = (int)asrk_div_up64(total4, per_block);
-        asrk_prof_begin_(PROF_ROWOPS, s);
-        hipLaunchKernelGGL(colsum_narrow_kernel, dim3(blocks), dim3(256), 0, s, X, total4, N / 4, out, per_block);
-        asrk_prof_end_(PROF_ROWOPS, s);
-        ASRK_LAUNCH_CHECK();
-        return ASRK_OK;
-    }
-    const int gx = asrk_div_up(N, vec ? 256 : 64);
-    int chunks = asrk_div_up(vec ? 2048 : 1024, gx);
-    if (chunks > asrk_div_up(M, 32)) chunks = asrk_div_up(M, 32);
-    // deterministic: ONE row chunk per column block - the block's fixed-order sum is the only value added to out[c]
-    if (chunks < 1 || asrk_knobs_().get(asrk_knobs_().deterministic, 0)) chunks = 1;
-    const int rpc = asrk_div_up(M, chunks);
-    chunks = asrk_div_up(M, rpc);
+    const rowops_plan::ColsumPlan pl = rowops_plan::colsum_plan(X, M, N, ldx);
+    const dim3 g(pl.gx, pl.gy);
     asrk_prof_begin_(PROF_ROWOPS, s);
-    if (vec)
-        hipLaunchKernelGGL(colsum_vec_kernel, dim3(gx, chunks), dim3(256), 0, s, X, M, N, ldx, out, rpc);
+    if (pl.variant == 2)
+        hipLaunchKernelGGL(colsum_narrow_kernel, g, dim3(256), 0, s, X, pl.total4, N / 4, out, pl.per_block);
+    else if (pl.variant == 1)
+        hipLaunchKernelGGL(colsum_vec_kernel, g, dim3(256), 0, s, X, M, N, ldx, out, pl.rpc);
     else
-        hipLaunchKernelGGL(colsum_kernel, dim3(gx, chunks), dim3(256), 0, s, X, M, N, ldx, out, rpc);
+        hipLaunchKernelGGL(colsum_kernel, g, dim3(256), 0, s, X, M, N, ldx, out, pl.rpc);
     asrk_prof_end_(PROF_ROWOPS, s);
     ASRK_LAUNCH_CHECK();
     return ASRK_OK;
+}
+
+// what the four entries above and in norm.hip / optim.hip would launch: their own plan functions, no device call
+extern "C" int asrk_rowops_plan_info(int op, const void *const *ptrs, const int64_t *args, int64_t *info, int n) {
+    if (!info || n < ASRK_ROWOPS_PLAN_INFO_LEN) return ASRK_EINVAL;
+    for (int i = 0; i < n; ++i) info[i] = 0;
+    if (!args || (!ptrs && op != ASRK_ROWOPS_PLAN_LN_PARAM)) return ASRK_EINVAL;
+    const auto fits = [](int64_t v) { return v >= 0 && v <= 0x7fffffffll; };
+    switch (op) {
+    case ASRK_ROWOPS_PLAN_COPY3D: {
+        if (!fits(args[0]) || !fits(args[1]) || !fits(args[2])) return ASRK_EINVAL;
+        if (args[0] == 0 || args[1] == 0 || args[2] == 0) return ASRK_OK;
+        if (!ptrs[0] || !ptrs[1]) return ASRK_EINVAL;
+        const rowops_plan::Copy3dPlan pl = rowops_plan::copy3d_plan(ptrs[0], ptrs[1], (int)args[0], (int)args[1],
+                                                                    (int)args[2], args[3], args[4], args[5], args[6],
+                                                                    args[7] != 0);
+        info[0] = pl.variant; info[1] = 1; info[2] = pl.gx; info[3] = pl.gy; info[4] = pl.rpb; info[6] = pl.total;
+        return ASRK_OK;
+    }
+    case ASRK_ROWOPS_PLAN_COLSUM: {
+        if (!fits(args[0]) || !fits(args[1]) || !fits(args[2]) || args[2] < args[1]) return ASRK_EINVAL;
+        if (args[1] == 0) return ASRK_OK;
+        if (!ptrs[1] || (!ptrs[0] && args[0] > 0)) return ASRK_EINVAL;
+        info[7] = args[3] ? 0 : 1;
+        if (args[0] == 0) return ASRK_OK;
+        const rowops_plan::ColsumPlan pl = rowops_plan::colsum_plan(ptrs[0], (int)args[0], (int)args[1], (int)args[2]);
+        info[0] = pl.variant; info[1] = 1; info[2] = pl.gx; info[3] = pl.gy;
+        info[4] = pl.variant == 2 ? pl.per_block : pl.rpc;
+        info[5] = pl.chunks; info[6] = pl.total4;
+        return ASRK_OK;
+    }
+    case ASRK_ROWOPS_PLAN_DROPOUT: {
+        if (args[0] < 0) return ASRK_EINVAL;
+        if (args[0] == 0) return ASRK_OK;
+        if (!ptrs[0] || !ptrs[1]) return ASRK_EINVAL;
+        const rowops_plan::DropoutPlan pl = rowops_plan::dropout_plan(ptrs[0], ptrs[1], args[0]);
+        info[0] = pl.variant; info[1] = 1; info[2] = pl.grid; info[3] = 1; info[6] = pl.nq;
+        return ASRK_OK;
+    }
+    case ASRK_ROWOPS_PLAN_ADADELTA: {
+        if (args[0] < 0) return ASRK_EINVAL;
+        if (args[0] == 0) return ASRK_OK;
+        if (!ptrs[0] || !ptrs[1] || !ptrs[2] || !ptrs[3]) return ASRK_EINVAL;
+        const rowops_plan::AdadeltaPlan pl = rowops_plan::adadelta_plan(ptrs[0], ptrs[1], ptrs[2], ptrs[3], args[0]);
+        info[0] = pl.variant; info[1] = 1; info[2] = pl.grid; info[3] = 1; info[6] = pl.items;
+        return ASRK_OK;
+    }
+    case ASRK_ROWOPS_PLAN_LN_PARAM: {
+        if (!fits(args[0]) || !fits(args[1]) || args[1] == 0) return ASRK_EINVAL;
+        if (args[0] == 0) return ASRK_OK;
+        const rowops_plan::LnParamPlan pl = rowops_plan::ln_param_plan((int)args[0], (int)args[1]);
+        info[1] = 1; info[2] = pl.gx; info[3] = pl.gy; info[4] = pl.rpc; info[5] = pl.gy;
+        return ASRK_OK;
+    }
+    default:
+        return ASRK_EINVAL;
+    }
 }
 
 extern "C" int asrk_tanh_fwd_f32(const float *x, float *y, int64_t n, void *stream) {

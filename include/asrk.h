@@ -167,6 +167,37 @@ int asrk_copy3d_f32(const float *src, float *dst, int n0, int n1, int n2,
 int asrk_colsum_f32(const float *X, int M, int N, int ldx, float *out, int accumulate,
                     void *stream);
 
+/* What asrk_copy3d_f32, asrk_colsum_f32, asrk_dropout_f32, asrk_adadelta_step_f32 and the parameter-gradient launch of
+ * asrk_layer_norm_bwd_f32 would launch for their arguments, from the plan functions the entries themselves call
+ * (csrc/rowops_plan.h); host only, no device call, runs without a GPU.  Pointers are looked at for their alignment and
+ * never read.  ptrs / args per op:
+ *   COPY3D    ptrs {src, dst}                      args {n0, n1, n2, s_stride0, s_stride1, d_stride0, d_stride1, accumulate}
+ *   COLSUM    ptrs {X, out}                        args {M, N, ldx, accumulate}
+ *   DROPOUT   ptrs {x, y}                          args {n}
+ *   ADADELTA  ptrs {param, grad, square_avg, acc}  args {n}
+ *   LN_PARAM  ptrs unused (may be NULL)            args {rows, cols}
+ * ASRK_EINVAL: info == NULL, n < ASRK_ROWOPS_PLAN_INFO_LEN, an unknown op, and whatever the entry itself refuses (a
+ * negative size, ldx < N, a NULL pointer it would read); info[0..n) is zeroed first whenever info and n are valid.
+ * Otherwise ASRK_OK and
+ *   [0] variant.  copy3d: 0 / 1 generic kernel, 4-byte lanes, copy / accumulate; 2 / 3 generic kernel, 16-byte lanes;
+ *       4 / 5 wide-row kernel (16-byte lanes, rows of >= 64 of them).  colsum: 0 scalar, 1 16-byte columns, 2 narrow
+ *       contiguous stream (ldx == N in {4, 8, 16, 32, 64, 128}, M >= 4096).  dropout, adadelta: 0 scalar, 1 16-byte.
+ *   [1] kernel launches (0: an empty problem; every other field but [7] is 0 then)
+ *   [2], [3] grid x, y
+ *   [4] copy3d wide-row kernel: rows per workgroup; colsum: rows per chunk (narrow: 16-byte pieces per workgroup, a
+ *       multiple of 2048); LN_PARAM: rows per chunk, a multiple of 4
+ *   [5] colsum, LN_PARAM: the workgroups whose sums meet in one output element (1 under ASRK_DETERMINISTIC)
+ *   [6] work items: copy3d elements or 16-byte pieces (generic kernel), colsum narrow 16-byte pieces, dropout quads,
+ *       adadelta elements or 16-byte pieces
+ *   [7] colsum: 1 = out is zeroed first (accumulate == 0) */
+#define ASRK_ROWOPS_PLAN_INFO_LEN 8
+#define ASRK_ROWOPS_PLAN_COPY3D 0
+#define ASRK_ROWOPS_PLAN_COLSUM 1
+#define ASRK_ROWOPS_PLAN_DROPOUT 2
+#define ASRK_ROWOPS_PLAN_ADADELTA 3
+#define ASRK_ROWOPS_PLAN_LN_PARAM 4
+int asrk_rowops_plan_info(int op, const void *const *ptrs, const int64_t *args, int64_t *info, int n);
+
 /* elementwise helpers (activation epilogues that are not fused into a GEMM) */
 int asrk_tanh_fwd_f32(const float *x, float *y, int64_t n, void *stream);
 /* dx = dy * (1 - y^2) */
