@@ -93,6 +93,10 @@ class Solver(BaseSolver):
             self.log.close()
 
     def validate(self):
+        with self.averaged_weights():           # hparas.average: scores and checkpoints of the averaged weights
+            self._validate()
+
+    def _validate(self):
         self.poll_device_errors(force=True)     # a validation score / checkpoint of parameters that are known good
         self.model.eval()
         dev_loss = []

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "rowops_plan.h"
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -123,6 +124,11 @@ __global__ __launch_bounds__(256) void multi_step_kernel(MultiArgs a) {
     }
 }
 
+// ~4 elements per thread, at most 2048 blocks per tensor
+inline int step_blocks_of(int64_t n) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(asrk_div_up64(n, 1024), 2048));
+}
+
 template <int OP>
 int multi_launch(int count, float *const *params, const float *const *grads, float *const *st0,
                  float *const *st1, const int64_t *numel, const float (&h)[8], const float *coef,
@@ -151,12 +157,202 @@ int multi_launch(int count, float *const *params, const float *const *grads, flo
             a.p[k] = params[t]; a.g[k] = grads[t]; a.s0[k] = st0[t]; a.s1[k] = st1[t];
             a.n[k] = numel[t];
             a.blk0[k] = blocks;
-            // ~4 elements per thread, at most 2048 blocks per tensor
-            blocks += (int)std::max<int64_t>(1, std::min<int64_t>(asrk_div_up64(numel[t], 1024), 2048));
+            blocks += step_blocks_of(numel[t]);
         }
         if (a.count == 0) continue;
         a.blk0[a.count] = blocks;
         hipLaunchKernelGGL((multi_step_kernel<OP>), dim3(blocks), dim3(256), 0, s, a);
+        ASRK_LAUNCH_CHECK();
+    }
+    asrk_prof_end_(PROF_OPTIM, s);
+    return ASRK_OK;
+}
+
+// ---- extended multi-tensor step: weight decay and a running average of the weights inside the same pass.
+// DECAY 0 none, 1 L2 (torch.optim.Adadelta / Adam(weight_decay=): g' += wd * p after clipping), 2 decoupled
+// (torch.optim.AdamW: p *= 1 - lr * wd before the update; the table carries that factor, formed in double on the
+// host as torch forms it).  AVG 1: e += w * (p_new - e) on the value that was just stored (one read and one write of
+// e, 8 B per element; a launch of its own would read p again).  Compiled per option: a disabled one costs no load
+// and no branch in the loop.  A tensor without an average in an AVG launch has e == NULL (uniform per workgroup).
+struct MultiArgsExt {
+    float *p[MT_MAX];
+    const float *g[MT_MAX];
+    float *s0[MT_MAX];
+    float *s1[MT_MAX];
+    float *e[MT_MAX];
+    long long n[MT_MAX];
+    float wd[MT_MAX];       // DECAY 1: lambda_t; DECAY 2: 1 - lr * lambda_t
+    int blk0[MT_MAX + 1];
+    int count;
+    float h[8];             // as MultiArgs
+    float w;                // weight of the new iterate in the average
+    const float *coef;
+};
+
+// one rounding per operation (the build has -ffp-contract=off): the fused kernel and avg_kernel give the same bits
+__device__ __forceinline__ float avg_of(float e, float p, float w) { return e + w * (p - e); }
+
+template <int OP, int DECAY, int AVG>
+__global__ __launch_bounds__(256) void multi_step_ext_kernel(MultiArgsExt a) {
+    if (skip_of(a.coef)) return;
+    int t = 0;
+    while (t + 1 < a.count && (int)blockIdx.x >= a.blk0[t + 1]) ++t;
+    const int nb = a.blk0[t + 1] - a.blk0[t], b = blockIdx.x - a.blk0[t];
+    float *__restrict__ p = a.p[t];
+    const float *__restrict__ g = a.g[t];
+    float *__restrict__ s0 = a.s0[t];
+    float *__restrict__ s1 = a.s1[t];
+    float *__restrict__ e = AVG ? a.e[t] : nullptr;
+    const long long n = a.n[t];
+    const float c = clip_of(a.coef), wd = a.wd[t];
+    const long long stride = (long long)nb * 256;
+    // the arithmetic of multi_step_kernel in its order, the options around it
+    for (long long i = (long long)b * 256 + threadIdx.x; i < n; i += stride) {
+        float pi = p[i];
+        float gr = g[i] * c;
+        // one rounding, as torch's CPU grad.add(param, alpha = wd): where g' is close to -wd * p the sum cancels, and a
+        // rounded product leaves it 3 x as far from float64 as torch's own float32 run (acc_delta, first step)
+        if (DECAY == 1) gr = __fmaf_rn(wd, pi, gr);
+        if (DECAY == 2) pi = pi * wd;
+        if (OP == 0) {
+            const float s = s0[i] * a.h[1] + a.h[2] * gr * gr;
+            const float delta = sqrtf(s1[i] + a.h[3]) / sqrtf(s + a.h[3]) * gr;
+            s0[i] = s;
+            s1[i] = s1[i] * a.h[1] + a.h[2] * delta * delta;
+            pi = pi - a.h[0] * delta;
+        } else {
+            const float mi = s0[i] + (gr - s0[i]) * a.h[1];
+            const float vi = s1[i] * a.h[2] + a.h[3] * gr * gr;
+            s0[i] = mi;
+            s1[i] = vi;
+            pi = pi - a.h[0] * (mi / (sqrtf(vi) / a.h[5] + a.h[4]));
+        }
+        p[i] = pi;
+        if (AVG) {
+            if (e) e[i] = avg_of(e[i], pi, a.w);
+        }
+    }
+}
+
+inline bool bad_weight(double w) { return !(w >= 0.0 && w <= 1.0); }          // NaN fails both comparisons
+
+template <int OP>
+int multi_launch_ext(int count, float *const *params, const float *const *grads, float *const *st0,
+                     float *const *st1, const int64_t *numel, const float (&h)[8], double lr, const float *coef,
+                     const float *weight_decay, int decay_mode, float *const *avg, double avg_weight, hipStream_t s) {
+    // the whole table before the first launch, as multi_launch
+    bool decays = decay_mode == 2, averages = false;
+    for (int t = 0; t < count; ++t) {
+        if (numel[t] < 0) return ASRK_EINVAL;
+        if (numel[t] > 0 && (!params[t] || !grads[t] || !st0[t] || !st1[t])) return ASRK_EINVAL;
+        if (weight_decay) {
+            if (!(weight_decay[t] >= 0.f) || !std::isfinite(weight_decay[t])) return ASRK_EINVAL;
+            if (decay_mode != 0 && numel[t] > 0 && weight_decay[t] != 0.f) decays = true;
+        }
+        if (avg && avg[t] && numel[t] > 0) averages = true;
+    }
+    const int DECAY = decays ? decay_mode : 0;
+    double bytes = 0.0;
+    for (int t = 0; t < count; ++t) bytes += (28.0 + (avg && avg[t] ? 8.0 : 0.0)) * (double)numel[t];
+    asrk_prof_work_(PROF_OPTIM, bytes);
+    asrk_prof_begin_(PROF_OPTIM, s);
+    for (int t = 0; t < count;) {
+        MultiArgsExt a;
+        a.count = 0;
+        a.coef = coef;
+        a.w = (float)avg_weight;
+        for (int j = 0; j < 8; ++j) a.h[j] = h[j];
+        int blocks = 0;
+        for (; t < count && a.count < MT_MAX; ++t) {
+            if (numel[t] == 0) continue;
+            const int k = a.count++;
+            a.p[k] = params[t]; a.g[k] = grads[t]; a.s0[k] = st0[t]; a.s1[k] = st1[t];
+            a.e[k] = avg ? avg[t] : nullptr;
+            const double lam = weight_decay ? (double)weight_decay[t] : 0.0;
+            a.wd[k] = DECAY == 2 ? (float)(1.0 - lr * lam) : (float)lam;
+            a.n[k] = numel[t];
+            a.blk0[k] = blocks;
+            blocks += step_blocks_of(numel[t]);
+        }
+        if (a.count == 0) continue;
+        a.blk0[a.count] = blocks;
+#define ASRK_EXT_LAUNCH(D, A) \
+        hipLaunchKernelGGL((multi_step_ext_kernel<OP, D, A>), dim3(blocks), dim3(256), 0, s, a)
+        if (averages) {
+            if (DECAY == 0) ASRK_EXT_LAUNCH(0, 1);
+            else if (DECAY == 1) ASRK_EXT_LAUNCH(1, 1);
+            else ASRK_EXT_LAUNCH((OP == 1 ? 2 : 0), 1);       // decoupled + Adadelta is rejected by the entry
+        } else {
+            if (DECAY == 0) ASRK_EXT_LAUNCH(0, 0);
+            else if (DECAY == 1) ASRK_EXT_LAUNCH(1, 0);
+            else ASRK_EXT_LAUNCH((OP == 1 ? 2 : 0), 0);
+        }
+#undef ASRK_EXT_LAUNCH
+        ASRK_LAUNCH_CHECK();
+    }
+    asrk_prof_end_(PROF_OPTIM, s);
+    return ASRK_OK;
+}
+
+// ---- two tensor lists side by side: MODE 0 the average as a launch of its own (a = e, b = p, read-only), for
+// optimisers that are not fused; MODE 1 exchange a and b in place (averaged weights into the live model and back)
+struct PairArgs {
+    float *a[MT_MAX];
+    float *b[MT_MAX];
+    long long n[MT_MAX];
+    int blk0[MT_MAX + 1];
+    int count;
+    float w;
+    const float *coef;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void pair_kernel(PairArgs a) {
+    if (MODE == 0 && skip_of(a.coef)) return;
+    int t = 0;
+    while (t + 1 < a.count && (int)blockIdx.x >= a.blk0[t + 1]) ++t;
+    const int nb = a.blk0[t + 1] - a.blk0[t], b = blockIdx.x - a.blk0[t];
+    float *__restrict__ x = a.a[t];
+    float *__restrict__ y = a.b[t];
+    const long long n = a.n[t], stride = (long long)nb * 256;
+    for (long long i = (long long)b * 256 + threadIdx.x; i < n; i += stride) {
+        if (MODE == 0) {
+            x[i] = avg_of(x[i], y[i], a.w);
+        } else {
+            const float xi = x[i];
+            x[i] = y[i];
+            y[i] = xi;
+        }
+    }
+}
+
+template <int MODE>
+int pair_launch(int count, float *const *a, float *const *b, const int64_t *numel, float w, const float *coef,
+                hipStream_t s) {
+    for (int t = 0; t < count; ++t) {
+        if (numel[t] < 0) return ASRK_EINVAL;
+        if (numel[t] > 0 && (!a[t] || !b[t])) return ASRK_EINVAL;
+    }
+    double bytes = 0.0;
+    for (int t = 0; t < count; ++t) bytes += (MODE == 0 ? 12.0 : 16.0) * (double)numel[t];
+    asrk_prof_work_(PROF_OPTIM, bytes);
+    asrk_prof_begin_(PROF_OPTIM, s);
+    for (int t = 0; t < count;) {
+        PairArgs pa;
+        pa.count = 0;
+        pa.coef = coef;
+        pa.w = w;
+        int blocks = 0;
+        for (; t < count && pa.count < MT_MAX; ++t) {
+            if (numel[t] == 0) continue;
+            const int k = pa.count++;
+            pa.a[k] = a[t]; pa.b[k] = b[t]; pa.n[k] = numel[t];
+            pa.blk0[k] = blocks;
+            blocks += step_blocks_of(numel[t]);
+        }
+        if (pa.count == 0) continue;
+        pa.blk0[pa.count] = blocks;
+        hipLaunchKernelGGL((pair_kernel<MODE>), dim3(blocks), dim3(256), 0, s, pa);
         ASRK_LAUNCH_CHECK();
     }
     asrk_prof_end_(PROF_OPTIM, s);
@@ -281,6 +477,52 @@ extern "C" int asrk_adam_multi_f32(int count, float *const *params, const float 
                         (float)eps, (float)sqrt(bc2), 0.f, 0.f};
     return multi_launch<1>(count, params, grads, exp_avg, exp_avg_sq, numel, h, clip_coef,
                            (hipStream_t)stream);
+}
+
+extern "C" int asrk_adadelta_multi_ext_f32(int count, float *const *params, const float *const *grads,
+                                           float *const *square_avg, float *const *acc_delta,
+                                           const int64_t *numel, double lr, double rho, double eps,
+                                           const float *clip_coef, const float *weight_decay, int decay_mode,
+                                           float *const *avg, double avg_weight, void *stream) {
+    if (count < 0 || decay_mode < 0 || decay_mode > 1 || bad_weight(avg_weight)) return ASRK_EINVAL;   // no decoupled form
+    if (count == 0) return ASRK_OK;
+    if (!params || !grads || !square_avg || !acc_delta || !numel) return ASRK_EINVAL;
+    const float h[8] = {(float)lr, (float)rho, (float)(1.0 - rho), (float)eps, 0.f, 0.f, 0.f, 0.f};
+    return multi_launch_ext<0>(count, params, grads, square_avg, acc_delta, numel, h, lr, clip_coef, weight_decay,
+                               decay_mode, avg, avg_weight, (hipStream_t)stream);
+}
+
+extern "C" int asrk_adam_multi_ext_f32(int count, float *const *params, const float *const *grads,
+                                       float *const *exp_avg, float *const *exp_avg_sq, const int64_t *numel,
+                                       double lr, double beta1, double beta2, double eps, int64_t step,
+                                       const float *clip_coef, const float *weight_decay, int decay_mode,
+                                       float *const *avg, double avg_weight, void *stream) {
+    if (count < 0 || step < 1 || decay_mode < 0 || decay_mode > 2 || bad_weight(avg_weight)) return ASRK_EINVAL;
+    if (count == 0) return ASRK_OK;
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !numel) return ASRK_EINVAL;
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    const float h[8] = {(float)(lr / bc1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                        (float)eps, (float)sqrt(bc2), 0.f, 0.f};
+    return multi_launch_ext<1>(count, params, grads, exp_avg, exp_avg_sq, numel, h, lr, clip_coef, weight_decay,
+                               decay_mode, avg, avg_weight, (hipStream_t)stream);
+}
+
+extern "C" int asrk_avg_multi_f32(int count, float *const *avg, const float *const *params, const int64_t *numel,
+                                  double avg_weight, const float *clip_coef, void *stream) {
+    if (count < 0 || bad_weight(avg_weight)) return ASRK_EINVAL;
+    if (count == 0) return ASRK_OK;
+    if (!avg || !params || !numel) return ASRK_EINVAL;
+    // MODE 0 only reads its second list
+    return pair_launch<0>(count, avg, const_cast<float *const *>(params), numel, (float)avg_weight, clip_coef,
+                          (hipStream_t)stream);
+}
+
+extern "C" int asrk_swap_multi_f32(int count, float *const *a, float *const *b, const int64_t *numel, void *stream) {
+    if (count < 0) return ASRK_EINVAL;
+    if (count == 0) return ASRK_OK;
+    if (!a || !b || !numel) return ASRK_EINVAL;
+    return pair_launch<1>(count, a, b, numel, 0.f, nullptr, (hipStream_t)stream);
 }
 
 extern "C" size_t asrk_grad_norm_ws_bytes(int count, const int64_t *numel) {

@@ -45,31 +45,67 @@ def total_grad_norm(params):
     return grad_norm_and_coef(params, 1.0)[0]
 
 
+def tensor_decay(group, p):
+    """lambda_t of parameter p in `group`: the group's weight_decay where p.dim() >= the group's `decay_min_dim` (a key
+    only the wrapper of src/optim.py sets; absent = 0 = torch's behaviour, everything decays), else 0 - biases and
+    LayerNorm gains are exempt without splitting the group the solver clips as one"""
+    return float(group.get('weight_decay', 0)) if p.dim() >= int(group.get('decay_min_dim', 0)) else 0.0
+
+
 class _FusedMixin:
     _state_keys = ()
+    _decoupled = False          # group flag `decoupled_weight_decay` (torch.optim.AdamW); Adadelta has none
 
     def _launch_group(self, group, params, grads, st0, st1, numel, coef):
         raise NotImplementedError
+
+    def _launch_group_ext(self, group, params, grads, st0, st1, numel, coef, wd, mode, avg, weight):
+        raise NotImplementedError
+
+    def attach_average(self, tensors_by_param):
+        """{parameter: f32 tensor of its shape}: from the next step on the update kernel also moves each of these
+        towards the new value of its parameter, e += w * (p_new - e), w as set by set_average_weight.  A parameter
+        that is not in the mapping has no average; None or {} detaches."""
+        avg = dict(tensors_by_param or {})
+        for p, e in avg.items():
+            if not (e.is_cuda and e.dtype == torch.float32 and e.is_contiguous() and e.shape == p.shape):
+                raise _lib.AsrkError("weight average: a contiguous f32 GPU tensor of the parameter's shape expected")
+        self._average = avg
+
+    def set_average_weight(self, weight):
+        weight = float(weight)
+        if not 0.0 <= weight <= 1.0:
+            raise ValueError("average weight %r outside [0, 1]" % weight)
+        self._average_weight = weight
 
     @torch.no_grad()
     def step(self, closure=None, clip_coef=None, clip_groups=None):
         """clip_coef: optional device scalar max_norm / (total_norm + 1e-6).  All tensors of a
         param_group go to the device in ONE call (asrk_*_multi_f32).  clip_groups = k: only the first k param_groups
         are clipped (the reference clips the model's gradients, not a plug-in's: src/solver.py:84); the others take
-        their gradients as they are, but still skip the update when the coefficient is NaN."""
+        their gradients as they are, but still skip the update when the coefficient is NaN.
+        A group takes the extended entry (asrk_*_multi_ext_f32) only when one of its tensors decays
+        (weight_decay != 0, and p.dim() >= the group's `decay_min_dim` where the wrapper set that key), the decay is
+        decoupled, or an average is attached; every other group makes the plain call."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         k0, k1 = self._state_keys
+        average = getattr(self, '_average', None) or {}
         unclipped = None
         if clip_coef is not None and clip_groups is not None and clip_groups < len(self.param_groups):
             unclipped = clip_coef * 0 + 1        # 1, or NaN with the coefficient: the kernels' skip predicate
         for gi, group in enumerate(self.param_groups):
-            if group.get('weight_decay', 0) != 0 or group.get('maximize', False) or group.get('amsgrad', False):
-                raise NotImplementedError("fused step: weight_decay / maximize / amsgrad are not used by the "
-                                          "reference configs")
-            params, grads, st0, st1 = [], [], [], []
+            if group.get('maximize', False) or group.get('amsgrad', False):
+                raise NotImplementedError("fused step: maximize / amsgrad are not used by the reference configs")
+            lam = float(group.get('weight_decay', 0))
+            if lam < 0 or lam != lam or lam == float('inf'):
+                raise ValueError("weight_decay %r" % lam)
+            decoupled = bool(group.get('decoupled_weight_decay', False))
+            if decoupled and not self._decoupled:
+                raise NotImplementedError("fused step: decoupled weight decay is Adam's")
+            params, grads, st0, st1, wd, avg = [], [], [], [], [], []
             for p in group['params']:
                 if p.grad is None:
                     continue
@@ -86,12 +122,26 @@ class _FusedMixin:
                 grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
                 st0.append(st[k0])
                 st1.append(st[k1])
+                wd.append(tensor_decay(group, p))
+                avg.append(average.get(p))
             if not params:
                 continue
             numel = (ctypes.c_int64 * len(params))(*[p.numel() for p in params])
             coef = clip_coef if (clip_groups is None or gi < clip_groups) else unclipped
-            self._launch_group(group, params, _ptr_array(params), _ptr_array(grads), _ptr_array(st0),
-                               _ptr_array(st1), numel, coef)
+            has_avg = any(e is not None for e in avg)
+            if decoupled or has_avg or any(w != 0 for w in wd):
+                self._launch_group_ext(group, params, _ptr_array(params), _ptr_array(grads), _ptr_array(st0),
+                                       _ptr_array(st1), numel, coef, (ctypes.c_float * len(wd))(*wd),
+                                       2 if decoupled else 1,
+                                       (ctypes.c_void_p * len(avg))(*[None if e is None else e.data_ptr() for e in avg])
+                                       if has_avg else None,
+                                       getattr(self, '_average_weight', 0.0) if has_avg else 0.0)
+            else:
+                self._launch_group(group, params, _ptr_array(params), _ptr_array(grads), _ptr_array(st0),
+                                   _ptr_array(st1), numel, coef)
+        # the parameters changed through raw pointers (no version bump): split panels of them are stale from here on
+        from . import decoder_ops
+        decoder_ops.drop_weight_panels()
         return loss
 
     def clip_and_step(self, max_norm):
@@ -114,18 +164,27 @@ class FusedAdadelta(_FusedMixin, torch.optim.Adadelta):
                                                 float(group['rho']), float(group['eps']), _p(coef),
                                                 _stream()), "adadelta_multi")
 
+    def _launch_group_ext(self, group, params, pp, gp, s0, s1, numel, coef, wd, mode, avg, weight):
+        _lib.check(_L().asrk_adadelta_multi_ext_f32(len(params), pp, gp, s0, s1, numel, float(group['lr']),
+                                                    float(group['rho']), float(group['eps']), _p(coef), wd, mode, avg,
+                                                    float(weight), _stream()), "adadelta_multi_ext")
+
 
 class FusedAdam(_FusedMixin, torch.optim.Adam):
     _state_keys = ('exp_avg', 'exp_avg_sq')
+    _decoupled = True
 
-    def _launch_group(self, group, params, pp, gp, s0, s1, numel, coef):
-        b1, b2 = group['betas']
+    def _by_step(self, params):
         # one bias correction per call: tensors that joined the optimiser later (different step
         # counts) go in separate calls
         by_step = {}
         for i, p in enumerate(params):
             by_step.setdefault(int(self.state[p]['step'].item()), []).append(i)
-        for step, idx in by_step.items():
+        return by_step
+
+    def _launch_group(self, group, params, pp, gp, s0, s1, numel, coef):
+        b1, b2 = group['betas']
+        for step, idx in self._by_step(params).items():
             def sub(arr, ty=ctypes.c_void_p):
                 return (ty * len(idx))(*[arr[i] for i in idx])
             _lib.check(_L().asrk_adam_multi_f32(len(idx), sub(pp), sub(gp), sub(s0), sub(s1),
@@ -133,5 +192,25 @@ class FusedAdam(_FusedMixin, torch.optim.Adam):
                                                 float(b2), float(group['eps']), step, _p(coef), _stream()),
                        "adam_multi")
 
+    def _launch_group_ext(self, group, params, pp, gp, s0, s1, numel, coef, wd, mode, avg, weight):
+        b1, b2 = group['betas']
+        for step, idx in self._by_step(params).items():
+            def sub(arr, ty=ctypes.c_void_p):
+                return (ty * len(idx))(*[arr[i] for i in idx])
+            _lib.check(_L().asrk_adam_multi_ext_f32(len(idx), sub(pp), sub(gp), sub(s0), sub(s1),
+                                                    sub(numel, ctypes.c_int64), float(group['lr']), float(b1),
+                                                    float(b2), float(group['eps']), step, _p(coef),
+                                                    sub(wd, ctypes.c_float), mode, None if avg is None else sub(avg),
+                                                    float(weight), _stream()), "adam_multi_ext")
 
-FUSED = {'Adadelta': FusedAdadelta, 'Adam': FusedAdam}
+
+class FusedAdamW(_FusedMixin, torch.optim.AdamW):
+    """torch.optim.AdamW is Adam with the group flag decoupled_weight_decay = True: same state, same state_dict()"""
+    _state_keys = FusedAdam._state_keys
+    _decoupled = True
+    _by_step = FusedAdam._by_step
+    _launch_group = FusedAdam._launch_group
+    _launch_group_ext = FusedAdam._launch_group_ext
+
+
+FUSED = {'Adadelta': FusedAdadelta, 'Adam': FusedAdam, 'AdamW': FusedAdamW}

@@ -13,6 +13,7 @@ MI355X differences:
   * apex AMP (`--amp`) is rejected: the hot path is exact f32 by contract (BASELINE north_star).
 """
 import abc
+import contextlib
 import json
 import math
 import os
@@ -126,6 +127,9 @@ class BaseSolver():
             self.verbose('Exp. name : {}'.format(self.exp_name))
             self.verbose('Loading data... large corpus may took a while.')
         elif mode == 'test':
+            # taken out of the block (the testing solver hands it whole to BeamDecoder(**dcfg)): decode with the averaged
+            # weights where the checkpoint has them (the default), or `decode: {averaged: false}` for the live ones
+            self.decode_averaged = bool((config.get('decode') or {}).pop('averaged', True))
             os.makedirs(paras.outdir, exist_ok=True)
             self.ckpdir = os.path.join(paras.outdir, self.exp_name)
             # the training config fixes the acoustic features, text encoder and model
@@ -197,9 +201,16 @@ class BaseSolver():
         ''' Load ckpt if --load option is specified (reference: src/solver.py:93-125) '''
         if self.paras.load:
             ckpt = torch.load(self.paras.load, map_location=self.device if self.mode == 'train' else 'cpu')
-            self.model.load_state_dict(ckpt['model'])
+            # decoding takes the averaged weights where the checkpoint has them (`decode: {averaged: false}`: the live
+            # ones); a checkpoint without them decodes as it always did
+            avg_key = ''
+            if self.mode != 'train' and 'model_avg' in ckpt and getattr(self, 'decode_averaged', True):
+                avg_key = '_avg'
+                self.verbose('Averaged weights ({} average, {} updates) from the checkpoint'.format(
+                    ckpt['average']['mode'], ckpt['average']['k']))
+            self.model.load_state_dict(ckpt['model' + avg_key])
             if self.emb_decoder is not None:
-                self.emb_decoder.load_state_dict(ckpt['emb_decoder'])
+                self.emb_decoder.load_state_dict(ckpt['emb_decoder' + avg_key])
             metric, score = "None", 0.0
             for k, v in ckpt.items():
                 if type(v) is float:
@@ -207,6 +218,17 @@ class BaseSolver():
             if self.mode == 'train':
                 self.step = ckpt['global_step']
                 self.optimizer.load_opt_state_dict(ckpt['optimizer'])
+                avg = self._average()
+                if avg is not None and 'model_avg' in ckpt:
+                    if ckpt['average']['mode'] != avg.mode:
+                        raise ValueError('average.mode: the checkpoint holds a {!r} average, the config asks for {!r}'
+                                         .format(ckpt['average']['mode'], avg.mode))
+                    avg.load_averaged_state_dict(self.model, ckpt['model_avg'], 0)
+                    if self.emb_decoder is not None:
+                        avg.load_averaged_state_dict(self.emb_decoder, ckpt['emb_decoder_avg'], 1)
+                    avg.k = int(ckpt['average']['k'])
+                elif avg is not None:
+                    self.verbose('Checkpoint without averaged weights: the average starts afresh from the loaded weights')
                 self.verbose('Load ckpt from {}, restarting at step {} (recorded {} = {:.2f} %)'.format(
                     self.paras.load, self.step, metric, score))
             else:
@@ -215,6 +237,15 @@ class BaseSolver():
                     self.emb_decoder.eval()
                 self.verbose('Evaluation target = {} (recorded {} = {:.2f} %)'.format(
                     self.paras.load, metric, score))
+
+    def _average(self):
+        return getattr(getattr(self, 'optimizer', None), 'average', None)
+
+    def averaged_weights(self):
+        """context manager for validate(): the averaged weights in the live model where averaging is on and has
+        started (dev scores and the choice of best_*.pth are theirs), the live weights back bit-identical afterwards"""
+        avg = self._average()
+        return avg.applied() if avg is not None and avg.started() else contextlib.nullcontext()
 
     def verbose(self, msg):
         if self.paras.verbose and self.rank == 0:
@@ -262,6 +293,16 @@ class BaseSolver():
         }
         if self.emb_decoder is not None:
             full_dict['emb_decoder'] = self.emb_decoder.state_dict()
+        avg = self._average()
+        if avg is not None and avg.started():
+            # "model" stays the live weights (resuming is exact), the averages go beside it - the right way round
+            # also from inside applied(), where validation calls this with the averages in the live model
+            full_dict['model'] = avg.live_state_dict(self.model, 0)
+            full_dict['model_avg'] = avg.averaged_state_dict(self.model, 0)
+            if self.emb_decoder is not None:
+                full_dict['emb_decoder'] = avg.live_state_dict(self.emb_decoder, 1)
+                full_dict['emb_decoder_avg'] = avg.averaged_state_dict(self.emb_decoder, 1)
+            full_dict['average'] = {'k': avg.k, 'mode': avg.mode}
         torch.save(full_dict, ckpt_path)
         if show_msg:
             self.verbose("Saved checkpoint (step = {}, {} = {:.2f}) and status @ {}".

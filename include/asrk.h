@@ -941,6 +941,31 @@ int asrk_adam_multi_f32(int count, float *const *params, const float *const *gra
                         float *const *exp_avg, float *const *exp_avg_sq, const int64_t *numel,
                         double lr, double beta1, double beta2, double eps, int64_t step,
                         const float *clip_coef, void *stream);
+/* Extended multi-tensor forms: the step above plus weight decay and a running average of the weights in the same
+ * pass.  weight_decay: HOST array [count] of per-tensor lambda_t >= 0, or NULL (no decay).  decay_mode 0 ignores it;
+ * 1 = L2 as torch.optim.Adadelta / Adam(weight_decay=) define it (g' = min(coef, 1) * g + lambda_t * p, the decay
+ * added after clipping); 2 = decoupled as torch.optim.AdamW (p *= 1 - lr * lambda_t before the update, lr the call's
+ * learning rate; adam only).  avg: HOST array [count] of device pointers e_t or NULL; a NULL entry is a tensor without
+ * an average.  After the new p is stored: e += avg_weight * (p - e), avg_weight in [0, 1].  A NaN clip_coef leaves p,
+ * both states and e untouched.  With decay_mode 0 (or lambda_t = 0 everywhere) and no average the result is the plain
+ * call's bit for bit.
+ * asrk_avg_multi_f32: the same e update as a launch of its own (optimisers that are not fused), the same bits and the
+ * same NaN skip.  asrk_swap_multi_f32: exchange the tensors of two lists in place, one launch per 24 tensors.
+ * ASRK_EINVAL before any device call: count or numel < 0, NULL table, NULL pointer of a non-empty tensor (avg entries
+ * of the step calls excepted), lambda_t < 0 or not finite, avg_weight outside [0, 1] or not finite, decay_mode outside
+ * 0..2, decay_mode 2 with adadelta. */
+int asrk_adadelta_multi_ext_f32(int count, float *const *params, const float *const *grads,
+                                float *const *square_avg, float *const *acc_delta, const int64_t *numel,
+                                double lr, double rho, double eps, const float *clip_coef,
+                                const float *weight_decay, int decay_mode, float *const *avg, double avg_weight,
+                                void *stream);
+int asrk_adam_multi_ext_f32(int count, float *const *params, const float *const *grads, float *const *exp_avg,
+                            float *const *exp_avg_sq, const int64_t *numel, double lr, double beta1, double beta2,
+                            double eps, int64_t step, const float *clip_coef, const float *weight_decay,
+                            int decay_mode, float *const *avg, double avg_weight, void *stream);
+int asrk_avg_multi_f32(int count, float *const *avg, const float *const *params, const int64_t *numel,
+                       double avg_weight, const float *clip_coef, void *stream);
+int asrk_swap_multi_f32(int count, float *const *a, float *const *b, const int64_t *numel, void *stream);
 
 /* Global 2-norm of a list of gradient tensors and the clipping coefficient of clip_grad_norm_(params, max_norm)
  * (src/solver.py:84): norm_out[0] = sqrt(sum_t sum_i g_t[i]^2), coef_out[0] = max_norm / (norm + 1e-6) (either may be
